@@ -12,17 +12,22 @@ config SURVEY §8 d3 names -- every 2^22-point MSM is split into contiguous poin
 (plonkhip.dist.shard_range), rank r reads only its range, and the partial discrete logs of all
 K steps are finished by plonkhip.dist.finish_sharded: ONE RCCL all-reduce SUM + the log -> point
 map (+ the gathered serial fold for MSMs with irregular encodings).  --weak: every rank owns a
-2^22-point shard of an N * 2^22-point MSM instead.  After timing, rank 0 recomputes the first
-MSM on one GPU and (strong, 2^22) the sharded path runs the reference golden input
-tests/golden/msm.json large[7]; both results are reported.
+2^22-point shard of an N * 2^22-point MSM instead.
 
-Also reported (rank 0, `components`): one 2^22 MSM per launch, the 2^16-point MSM (config C2),
+A plain run does only that: set up, warm up, time the K steps, print the headline line
+(--dump-outputs DIR also writes the last step's results).  Everything below runs with --full.
+
+--full: after timing, rank 0 recomputes the first MSM on one GPU and (strong, 2^22) the sharded
+path runs the reference golden input tests/golden/msm.json large[7]; both results are reported
+(`checks`), with the kernel-level HBM roofline of the timed launch (`roofline`).
+
+Also reported with --full (rank 0, `components`): one 2^22 MSM per launch, the 2^16-point MSM (config C2),
 the 2^20 forward NTT (config C3) and poly_mul 2^19 x 2^19 with their rooflines, the 2^20-gate
 prove (C5: plain, preprocessed, and the pieces of its strong-scaled form; at N > 1 replicas on
 every GPU and one proof strong-scaled over up to 3 GPUs), and the reference CPU path timed on this
 host (MSM, schoolbook poly_mul, toy prove).
 
-    python bench.py [--gpus N --steps K --warmup W --log2n 22 --weak]
+    python bench.py [--gpus N --steps K --warmup W --log2n 22 --weak --full --dump-outputs DIR]
 """
 import argparse
 import json
@@ -76,7 +81,26 @@ def parse():
     ap.add_argument("--weak", action="store_true",
                     help="N > 1: every rank owns a full 2^log2n-point shard (default: strong, each "
                          "2^log2n-point MSM split over the ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else this bench measures or checks: the checks "
+                         "of the timed results (single-GPU recompute, the reference golden), the kernel-level "
+                         "roofline, the CPU baseline and the components (--components, --no-cpu-baseline, "
+                         "--cpu-seconds choose among them).  Without it the run sets up, warms up, times the "
+                         "steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32): msm_g1 = the step's --msm-batch commitments, one row "
+                         "{x, y, infinite} per MSM (plonkhip.dist.finish_sharded).  The inputs are seeded, so "
+                         "two builds run with the same arguments can be compared output for output")
     return ap.parse_args()
+
+
+def dump_outputs(path, g1_last):
+    """--dump-outputs: the last timed step's results as rank 0's caller receives them (finish_sharded's
+    uint8 [batch, 4] tensor of {x, y, infinite, 0}; the padding byte is not an output)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "msm_g1.npy"), g1_last[:, :3].cpu().numpy().astype(np.float32))
 
 
 KG16 = [[1, 2, 0], [68, 74, 0], [26, 45, 0], [65, 98, 0], [12, 32, 0], [32, 42, 0], [91, 35, 0], [18, 49, 0],
@@ -990,6 +1014,47 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, g1t[(K - 1) * B:K * B])
+
+    irregular = int(partials[:, 1].sum().item())
+    total_points = (n if strong or world == 1 else world * n) * B * K
+    value = total_points / elapsed / 1e6
+    line = {
+        "metric": "G1-MSM Mpoint/s + NTT Gelem/s; end-to-end prove ms at 2^20 gates",
+        "value": round(value, 1),
+        "unit": "Mpoint/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": W,
+        "ms_per_step": round(elapsed / K * 1e3, 5),
+        "higher_is_better": True,
+        "scaling": "weak" if args.weak else "strong",   # (N = 1: the mode the N > 1 runs use)
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic: SRS points kG (k uniform 1..16), HF scalars uniform 0..16, %d distinct "
+                "input sets (%d MiB per GPU) rotated so every step reads cold data, resident in HBM"
+                % (sets, sets * MSM_BYTES_PER_POINT * m >> 20),
+        "config": {"workload": "%d x 2^%d-point G1 MSMs (srs_eval_at_s) per step, one batched launch per GPU over %d "
+                               "distinct input sets; %s; ONE RCCL all-reduce of the partial logs of all K steps "
+                               "(plonkhip.dist.finish_sharded)" % (
+                                   B, args.log2n, B,
+                                   "each MSM point-range sharded over %d GPU(s) (%d points per GPU)" % (world, m)
+                                   if strong or world == 1 else
+                                   "every GPU owns a 2^%d-point shard of %d-GPU MSMs" % (args.log2n, world)),
+                   "points_per_msm": n if strong or world == 1 else world * n, "points_per_gpu": m,
+                   "msms_per_step": B, "msms_per_launch": B, "parallelism": "dp%d" % world},
+        **({"tuning": tuned} if tuned else {}),
+        "irregular_inputs": irregular,
+        "serial_fold_fallbacks": folded,
+    }
+    if not args.full:
+        # the plain run: nothing beyond what the headline needs
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- correctness of the timed results (outside the timed region)
     g1s = g1_bytes(g1t[:1])
@@ -1021,7 +1086,6 @@ def main():
         ops.launch(sp, 0, ss, 0, hi - lo, 1, rec)
         got, _ = finish_sharded(ops.records_to_partials(rec), n, ops, lambda j: (sp, ss))
         check["golden_2^22_reference"] = g1_bytes(got)[0].hex() == gold["out"]
-    irregular = int(partials[:, 1].sum().item())
 
     # Kernel-level timing for the roofline, on the stream the kernel runs on: one event pair
     # around L back-to-back launches of B MSMs (a pair around every launch would add its
@@ -1048,32 +1112,7 @@ def main():
     achieved = alg / (avg_ms * 1e-3) / 1e9
     traffic, kname = pmc_traffic(args.log2n, B, m)
 
-    total_points = (n if strong or world == 1 else world * n) * B * K
-    value = total_points / elapsed / 1e6
-    line = {
-        "metric": "G1-MSM Mpoint/s + NTT Gelem/s; end-to-end prove ms at 2^20 gates",
-        "value": round(value, 1),
-        "unit": "Mpoint/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": round(elapsed / K * 1e3, 5),
-        "higher_is_better": True,
-        "scaling": "weak" if args.weak else "strong",   # (N = 1: the mode the N > 1 runs use)
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic: SRS points kG (k uniform 1..16), HF scalars uniform 0..16, %d distinct "
-                "input sets (%d MiB per GPU) rotated so every step reads cold data, resident in HBM"
-                % (sets, sets * MSM_BYTES_PER_POINT * m >> 20),
-        "config": {"workload": "%d x 2^%d-point G1 MSMs (srs_eval_at_s) per step, one batched launch per GPU over %d "
-                               "distinct input sets; %s; ONE RCCL all-reduce of the partial logs of all K steps "
-                               "(plonkhip.dist.finish_sharded)" % (
-                                   B, args.log2n, B,
-                                   "each MSM point-range sharded over %d GPU(s) (%d points per GPU)" % (world, m)
-                                   if strong or world == 1 else
-                                   "every GPU owns a 2^%d-point shard of %d-GPU MSMs" % (args.log2n, world)),
-                   "points_per_msm": n if strong or world == 1 else world * n, "points_per_gpu": m,
-                   "msms_per_step": B, "msms_per_launch": B, "parallelism": "dp%d" % world},
+    line.update({
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "traffic": traffic, "kernel": kname,
@@ -1081,10 +1120,7 @@ def main():
                      "timing": "hipEvent pair around %d back-to-back launches on the kernel's "
                                "stream, opened after one primer launch is queued" % L},
         "checks": check,
-        **({"tuning": tuned} if tuned else {}),
-        "irregular_inputs": irregular,
-        "serial_fold_fallbacks": folded,
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         torch.cuda.synchronize()
         line["cpu_baseline"] = cpu_baseline(pts[first_set].cpu().numpy(), sc[first_set].cpu().numpy(),

@@ -19,12 +19,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_two_rank_strong_scaling_line():
-    """plain `python bench.py --gpus 2`, no external launcher: the bench starts its two ranks itself
+    """`python bench.py --gpus 2 --full`, no external launcher: the bench starts its two ranks itself
     (torch.distributed.run as a child, VERDICT r4 next #1) and the line says n_gpus 2"""
     env = dict(os.environ, PLK_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--msm-batch", "8", "--rotate-mib", "160", "--components", "prove,msm", "--no-cpu-baseline"]
+           "--msm-batch", "8", "--rotate-mib", "160", "--full", "--components", "prove,msm", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -47,12 +47,13 @@ def test_two_rank_strong_scaling_line():
 
 
 def _plain_bench_line(n, components, batch, rotate, steps=2, timeout=540):
-    """`python bench.py --gpus n` exactly as the driver's scaling run starts it (no launcher: the bench
+    """`python bench.py --gpus n --full`, started as the driver's scaling run starts it (no launcher: the bench
     spawns its n ranks), gloo so that n ranks share the one GPU of a test box; rank 0's line"""
     env = dict(os.environ, PLK_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", str(steps), "--warmup", "1",
-           "--msm-batch", str(batch), "--rotate-mib", str(rotate), "--components", components, "--no-cpu-baseline"]
+           "--msm-batch", str(batch), "--rotate-mib", str(rotate), "--full", "--components", components,
+           "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -88,7 +89,7 @@ def test_three_rank_split_proof():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
            "--master-addr", "127.0.0.1", "--master-port", "29563", os.path.join(ROOT, "bench.py"),
            "--gpus", "3", "--steps", "2", "--warmup", "1", "--msm-batch", "4", "--rotate-mib", "96",
-           "--components", "prove", "--no-cpu-baseline"]
+           "--full", "--components", "prove", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,9 +1,11 @@
-# rocprof A/B of the single-MSM form (PLK_MSM_HALF=0/1) inside the default bench
+# rocprof A/B of the single-MSM form (PLK_MSM_HALF=0/1) inside the full bench
+# (output directory: $OUT, default bench_out)
 set -e
 export TMPDIR=/tmp
-mkdir -p gpurun_out/hp
+O=${OUT:-bench_out}/hp
+mkdir -p $O
 for h in 0 1 0 1; do
-PLK_MSM_HALF=$h timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/hp/t -o run -- python3 bench.py --steps 20 --no-cpu-baseline > /dev/null 2>&1
-python3 tools/kstats.py gpurun_out/hp/t/run_results.db | grep "msm_dlog" | sed "s/^/half=$h /"
-rm -rf gpurun_out/hp/t
+PLK_MSM_HALF=$h timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/t -o run -- python3 bench.py --full --steps 20 --no-cpu-baseline > /dev/null 2>&1
+python3 tools/kstats.py $O/t/run_results.db | grep "msm_dlog" | sed "s/^/half=$h /"
+rm -rf $O/t
 done
