@@ -112,7 +112,12 @@ enum {
                                     ns: la*lb MACs for poly_mul, 300 per MSM point, ...) is at most this stays
                                     on the host; 32768 ~ one GPU round trip; 0: every call on the GPU.  The
                                     library reads it only through plk_get_option */
-  PLK_OPT_COUNT = 29
+  PLK_OPT_DIVIDE_FAST_MIN = 29,  /* poly_divide by a general canonical divisor (not constant, not lead x^m + d0;
+                                    lead in 1..16, nl >= dl): from (nl - dl + 1) * dl >= this value the
+                                    quotient comes from a Newton inverse over the exact poly_mul products
+                                    instead of the reference's loop on one GPU thread.  0: never, 1: whenever
+                                    eligible; default 256, the measured crossover */
+  PLK_OPT_COUNT = 30
 };
 int plk_set_option(int opt, int64_t value);   /* PLK_ERR_ARG: unknown option or value out of range */
 /* Diagnostics for the roofline tools: with PLK_OPT_NTT_LAUNCH_LOG = 1 every NTT pass launch
@@ -245,7 +250,10 @@ int plk_poly_eval_batch_dev(const uint8_t *const *d_polys, const size_t *lens, c
  *   quot: max(nl - dl + 1, 1) bytes, rem: min(dl - 1, nl) bytes (may be NULL when that is 0);
  *   *quot_len / *rem_len = lengths after the reference's trim (rem_len 0 when dl == 1).
  * Divisors x^m * lead + d0 (Z_H = x^n - 1, x - z, constants) run as parallel chain scans; any
- * other divisor, and non-canonical numerator bytes, run the reference's loop on the device.
+ * other canonical divisor of at least PLK_OPT_DIVIDE_FAST_MIN loop steps runs as a Newton inverse
+ * over exact poly_mul products (byte-identical: Euclidean division over GF(17) is unique); smaller
+ * ones, non-canonical divisors and non-canonical numerator bytes run the reference's loop on the
+ * device (one thread).
  * A zero divisor is PLK_ERR_ARG ("Division by zero polynomial in poly_divide"); a divisor lead
  * byte >= 17 is PLK_ERR_RANGE (the reference reads hf_inverses out of bounds). */
 int plk_poly_divide(const uint8_t *num, size_t nl, const uint8_t *den, size_t dl, uint8_t *quot, size_t *quot_len,
@@ -253,10 +261,17 @@ int plk_poly_divide(const uint8_t *num, size_t nl, const uint8_t *den, size_t dl
 /* device form: den stays a HOST array (classified on the host, copied into d_work when the
  * serial loop needs it); d_lens[0..1] receive the index + 1 of the last non-zero quotient /
  * remainder byte (0: all zero) over the untrimmed lengths above; d_work:
- * plk_poly_divide_workspace(nl, dl) bytes. */
+ * plk_poly_divide_workspace(nl, dl) bytes (sized for the Newton path of every shape that could take
+ * it, whatever PLK_OPT_DIVIDE_FAST_MIN is; it does depend on PLK_OPT_POLY_BLOCK_L / _S as
+ * plk_poly_mul_workspace does). */
 size_t plk_poly_divide_workspace(size_t nl, size_t dl);
 int plk_poly_divide_dev(const uint8_t *d_num, size_t nl, const uint8_t *den, size_t dl, uint8_t *d_quot,
                         uint8_t *d_rem, uint32_t *d_lens, void *d_work, void *stream);
+/* The path plk_poly_divide / plk_poly_divide_dev take for this divisor (a HOST array) and numerator
+ * length under the current options: 0 trivial (nl < dl), 1 constant, 2 binomial chain scans, 3 the
+ * reference's loop on one thread, 4 Newton inverse.  A zero divisor gives -PLK_ERR_ARG, a lead
+ * byte >= 17 -PLK_ERR_RANGE.  Host only: touches no device, works with no GPU present. */
+int plk_poly_divide_path(const uint8_t *den, size_t dl, size_t nl);
 
 /* Replaces matrix_mul (src/matrix.h:79-96): out[m x n] = a[m x k] b[k x n], row-major bytes,
  * sums by hf_add of hf_mul products. */

@@ -483,6 +483,7 @@ const OptDef kOpt[PLK_OPT_COUNT] = {
     {1, 0, 1, false},                          // PROVE_EVAL_AGG
     {0, 0, 1, false},                          // PROVE_GRAPH
     {32768, 0, 1ll << 40, false},              // DROPIN_HOST_WORK (read by include/plk_host.h only)
+    {256, 0, 1ll << 62, false},                // DIVIDE_FAST_MIN (measured crossover)
 };
 struct Opts {
   std::atomic<int64_t> v[PLK_OPT_COUNT];
@@ -993,6 +994,8 @@ int plk_poly_eval(const uint8_t* p, size_t len, uint8_t x, uint8_t* y) {
 }
 
 size_t plk_poly_divide_workspace(size_t nl, size_t dl) { return plk_poly_divide_workspace_bytes(nl, dl); }
+
+int plk_poly_divide_path(const uint8_t* den, size_t dl, size_t nl) { return plk_poly_divide_classify(den, dl, nl); }
 
 int plk_poly_divide_dev(const uint8_t* d_num, size_t nl, const uint8_t* den, size_t dl, uint8_t* d_quot,
                         uint8_t* d_rem, uint32_t* d_lens, void* d_work, void* stream) {

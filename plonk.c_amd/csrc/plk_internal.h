@@ -186,6 +186,7 @@ void plk_wave_free_coltabs(void);
 int plk_poly_eval_batch_launch(const uint8_t* const* polys, const uint64_t* lens, const uint8_t* xs, int nj,
                                uint8_t* d_y, void* d_tick, hipStream_t st);
 size_t plk_poly_divide_workspace_bytes(uint64_t nl, uint64_t dl);
+int plk_poly_divide_classify(const uint8_t* den, uint64_t dl, uint64_t nl);   // host only: the path, or -PLK_ERR_*
 int plk_poly_divide_launch(const uint8_t* d_num, uint64_t nl, const uint8_t* den, uint64_t dl, uint8_t* d_q,
                            uint8_t* d_rem, uint32_t* d_lens, void* d_work, hipStream_t st);
 int plk_matrix_mul_launch(const uint8_t* d_a, uint64_t m, uint64_t k, const uint8_t* d_b, uint64_t n, uint8_t* d_out,

@@ -173,7 +173,8 @@ __device__ uint32_t fin_trim(const uint8_t* __restrict__ p, uint64_t len, uint32
 
 // ONE launch after the division kernels: the reference's loop when it is needed (mode 1: always,
 // the divisor copied to the device; mode 2: only when the chain scans flagged non-canonical
-// numerator bytes, binomial divisor by its two bytes), then the trimmed lengths of q and rem
+// numerator bytes, binomial divisor by its two bytes -- or, behind the Newton path, the divisor's
+// device copy), then the trimmed lengths of q and rem
 // (src/poly.h:158-170) -- three launches (serial re-run + two trims) folded into one.
 __global__ __launch_bounds__(1024) void div_finish_kernel(const uint8_t* __restrict__ num, uint64_t nl,
                                                          const uint8_t* __restrict__ den, uint64_t dl, uint32_t d0,
@@ -336,6 +337,174 @@ __global__ __launch_bounds__(256) void div_const_kernel(const uint8_t* __restric
 }
 
 // ---------------------------------------------------------------------------------------
+// General divisors: Newton inverse over the exact products.  With m = dl - 1,
+// k = nl - m, f = rev(den) (f[0] = lead), a = rev(num): g = f^-1 mod x^k, rev(q) = a g mod x^k,
+// rem = num - q den mod x^m.  On canonical bytes that is the reference's loop (Euclidean
+// division is unique); a numerator byte >= 17 sets the flag and div_finish_kernel re-runs the loop.
+// The kernels below are the glue between the products: 16 bytes per thread at any address (num, q
+// and rem are the caller's buffers), truncation and zero padding done here, not by memsets.
+// ---------------------------------------------------------------------------------------
+struct __attribute__((packed, aligned(1))) U4u {   // 16 bytes at any address (caller buffers)
+  uint32_t x, y, z, w;
+};
+// non-zero when some byte of w is >= 17
+__device__ __forceinline__ uint32_t bad4(uint32_t w) {
+  return (((w & 0x7F7F7F7Fu) + 0x6F6F6F6Fu) | w) & 0x80808080u;
+}
+// per byte (17 - b) % 17, bytes < 17
+__device__ __forceinline__ uint32_t neg4(uint32_t w) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int s = 0; s < 32; s += 8) {
+    const uint32_t b = (w >> s) & 0xFFu;
+    r |= (b ? HP - b : 0u) << s;
+  }
+  return r;
+}
+// per byte (a + 17 - b) % 17, b < 17 (a >= 17 gives some byte: the flagged re-run overwrites it)
+__device__ __forceinline__ uint32_t sub4(uint32_t a, uint32_t b) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int s = 0; s < 32; s += 8) r |= ((((a >> s) & 0xFFu) + HP - ((b >> s) & 0xFFu)) % HP) << s;
+  return r;
+}
+
+// dst[j] = src[n - 1 - j], j < n: 16 bytes per thread, reversed by byte permutes; check: a byte
+// >= 17 sets the flag.  Job blockIdx.y (the numerator's top k bytes and the divisor in one launch).
+struct RevJob {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t n;
+  int check;
+};
+struct RevJobs {
+  RevJob j[2];
+  uint32_t* flag;
+};
+__global__ __launch_bounds__(256) void div_reverse_kernel(RevJobs J) {
+  const RevJob jb = J.j[blockIdx.y];
+  const uint64_t chunks = (jb.n + 15) >> 4;
+  uint32_t bad = 0;
+  for (uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (uint64_t)gridDim.x * 256) {
+    const uint64_t j0 = c << 4;
+    if (j0 + 16 <= jb.n) {
+      const U4u v = *reinterpret_cast<const U4u*>(jb.src + (jb.n - 16 - j0));
+      bad |= bad4(v.x) | bad4(v.y) | bad4(v.z) | bad4(v.w);
+      U4u o;
+      o.x = __builtin_bswap32(v.w);
+      o.y = __builtin_bswap32(v.z);
+      o.z = __builtin_bswap32(v.y);
+      o.w = __builtin_bswap32(v.x);
+      *reinterpret_cast<U4u*>(jb.dst + j0) = o;
+    } else {
+      for (uint64_t j = j0; j < jb.n; j++) {
+        const uint32_t b = jb.src[jb.n - 1 - j];
+        bad |= b >= HP;
+        jb.dst[j] = (uint8_t)b;
+      }
+    }
+  }
+  if (jb.check && bad) atomicOr(J.flag, 1u);
+}
+
+// g[0, B) = f^-1 mod x^B in one block, g and f in LDS (B <= INV_B0; f zero past fl).  Thread i
+// owns acc_i = sum_{j >= 1} f[j] g[i - j] over the g known so far and g[i] = -inv(f[0]) acc_i.
+// 64 coefficients at a time: their wave solves its triangle with lane broadcasts (no barrier),
+// then every later thread adds the 64 new terms -- B / 64 barriers instead of B reductions.
+constexpr int INV_B0 = 1024;
+__global__ __launch_bounds__(INV_B0) void div_base_inverse_kernel(const uint8_t* __restrict__ f, uint32_t fl,
+                                                                  uint32_t B, uint8_t* __restrict__ g) {
+  __shared__ __attribute__((aligned(16))) uint8_t sf[INV_B0], sg[INV_B0];
+  const uint32_t tid = threadIdx.x, lane = tid & (PLK_WAVE - 1);
+  sf[tid] = tid < fl ? f[tid] : (uint8_t)0;
+  sg[tid] = 0;
+  __syncthreads();
+  const uint32_t inv0 = c_hinv17[sf[0]], ninv = (HP - inv0) % HP;
+  uint32_t acc = 0;
+  for (uint32_t base = 0; base < B; base += PLK_WAVE) {
+    if ((tid & ~(uint32_t)(PLK_WAVE - 1)) == base) {   // (wave-uniform)
+      uint32_t gi = 0;
+      for (uint32_t s = 0; s < PLK_WAVE; s++) {
+        // final in lane s (acc < 17 + 63 * 256); s is uniform: a v_readlane, not an LDS permute
+        const uint32_t mine = tid == 0 ? inv0 : ninv * acc % HP;
+        const uint32_t gs = (uint32_t)__builtin_amdgcn_readlane((int)mine, (int)s);
+        if (lane == s) gi = gs;
+        if (lane > s) acc += sf[lane - s] * gs;
+      }
+      sg[tid] = (uint8_t)gi;
+    }
+    __syncthreads();
+    if (tid >= base + PLK_WAVE && tid < B) {
+      const uint32_t* g4 = reinterpret_cast<const uint32_t*>(sg + base);   // (broadcast reads, 4 g per word)
+      const uint8_t* fw = sf + (tid - base);
+#pragma unroll 4
+      for (uint32_t s = 0; s < PLK_WAVE; s += 4) {
+        const uint32_t w = g4[s >> 2];
+        acc += fw[-(int)s] * (w & 0xFFu) + fw[-(int)s - 1] * ((w >> 8) & 0xFFu) + fw[-(int)s - 2] * ((w >> 16) & 0xFFu) +
+               fw[-(int)s - 3] * (w >> 24);
+      }
+      acc %= HP;
+    }
+  }
+  if (tid < B) g[tid] = sg[tid];
+}
+
+// One Newton step t -> n2 = min(2t, k): with e = f g mod x^n2 = 1 + x^t e', the new upper half
+// is g[t, n2) = (g[0, t) (-e'))[0, n2 - t).  This kernel forms E = -e' from the first product
+// P = f[0, fl2) g[0, t) (pl bytes; zero past them): E[i] = -P[t + i], i < cnt; the second product
+// writes g[t, ..) itself.
+__global__ __launch_bounds__(256) void div_newton_neg_kernel(const uint8_t* __restrict__ P, uint64_t pl, uint64_t t,
+                                                             uint8_t* __restrict__ E, uint64_t cnt) {
+  const uint64_t chunks = (cnt + 15) >> 4;
+  for (uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (uint64_t)gridDim.x * 256) {
+    const uint64_t i0 = c << 4;
+    if (i0 + 16 <= cnt && t + i0 + 16 <= pl) {
+      const U4u v = *reinterpret_cast<const U4u*>(P + t + i0);
+      U4u o;
+      o.x = neg4(v.x);
+      o.y = neg4(v.y);
+      o.z = neg4(v.z);
+      o.w = neg4(v.w);
+      *reinterpret_cast<U4u*>(E + i0) = o;
+    } else {
+      for (uint64_t i = i0; i < cnt && i < i0 + 16; i++) {
+        const uint32_t b = t + i < pl ? P[t + i] : 0u;
+        E[i] = (uint8_t)(b ? HP - b : 0u);
+      }
+    }
+  }
+}
+
+// rem[i] = num[i] - R[i] mod 17, i < m (R = q den's low bytes, workspace); checks num[0, m)
+__global__ __launch_bounds__(256) void div_rem_sub_kernel(const uint8_t* __restrict__ num, const uint8_t* __restrict__ R,
+                                                          uint64_t m, uint8_t* __restrict__ rem,
+                                                          uint32_t* __restrict__ flag) {
+  const uint64_t chunks = (m + 15) >> 4;
+  uint32_t bad = 0;
+  for (uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (uint64_t)gridDim.x * 256) {
+    const uint64_t i0 = c << 4;
+    if (i0 + 16 <= m) {
+      const U4u a = *reinterpret_cast<const U4u*>(num + i0);
+      const U4u r = *reinterpret_cast<const U4u*>(R + i0);
+      bad |= bad4(a.x) | bad4(a.y) | bad4(a.z) | bad4(a.w);
+      U4u o;
+      o.x = sub4(a.x, r.x);
+      o.y = sub4(a.y, r.y);
+      o.z = sub4(a.z, r.z);
+      o.w = sub4(a.w, r.w);
+      *reinterpret_cast<U4u*>(rem + i0) = o;
+    } else {
+      for (uint64_t i = i0; i < m; i++) {
+        const uint32_t a = num[i];
+        bad |= a >= HP;
+        rem[i] = (uint8_t)((a + HP - R[i]) % HP);
+      }
+    }
+  }
+  if (bad) atomicOr(flag, 1u);
+}
+
+// ---------------------------------------------------------------------------------------
 // matrices (row-major bytes, src/matrix.h).  matrix_mul: sum = hf_add(sum, hf_mul(a, b)) per
 // element (one thread each).  matrix_inv: Gauss-Jordan on [M | I] exactly as
 // matrix_gauss_jordan (src/matrix.h:100-147) -- pivot search, swaps, normalisation and
@@ -443,7 +612,7 @@ int plk_poly_eval_batch_launch(const uint8_t* const* polys, const uint64_t* lens
   return PLK_OK;
 }
 
-size_t plk_poly_divide_workspace_bytes(uint64_t nl, uint64_t dl) {
+static size_t divide_base_bytes(uint64_t nl, uint64_t dl) {
   // den copy + flag/length words + scan block aggregates (long chains)
   const uint64_t m = dl ? dl - 1 : 0;
   const uint64_t lq = nl >= dl ? nl - m : 0;
@@ -453,27 +622,144 @@ size_t plk_poly_divide_workspace_bytes(uint64_t nl, uint64_t dl) {
   return 256 + ((dl + 15) & ~15ull) + 4 * (chains * nblk + 16) + ((nl + 15) & ~15ull);   // + the serial remainder
 }
 
+// The Newton path's shapes and its buffers behind the base workspace (offsets from d_work, each
+// a multiple of 256): g (the second product of a step writes g[t, ..) itself, t + n2 - 1 <= 2k
+// bytes), the reversed operands, one product output, E, and the largest product's workspace.
+struct NewtonPlan {
+  // fl = min(dl, k) coefficients of f are ever read; B: the base inverse's size, k halved (rounding
+  // up) until it is <= INV_B0, so that the doublings end at k with no short last step
+  uint64_t m, k, fl, B;
+  size_t o_g, o_ar, o_f, o_p, o_e, o_mw, total;
+};
+static uint64_t up256(uint64_t v) { return (v + 255) & ~255ull; }
+static bool newton_shape(uint64_t nl, uint64_t dl) { return dl >= 3 && nl >= dl && nl <= (1ull << 31); }
+static NewtonPlan newton_plan(uint64_t nl, uint64_t dl) {
+  NewtonPlan p{};
+  p.m = dl - 1;
+  p.k = nl - p.m;
+  p.fl = dl < p.k ? dl : p.k;
+  for (p.B = p.k; p.B > (uint64_t)INV_B0;) p.B = (p.B + 1) / 2;
+  const uint64_t kq = p.k < p.m ? p.k : p.m;
+  uint64_t pout = 2 * p.k - 1, mw = plk_poly_mul_workspace_bytes(p.k, p.k);   // rev(q) = a g
+  auto product = [&](uint64_t la, uint64_t lb, bool to_p) {
+    if (to_p && la + lb - 1 > pout) pout = la + lb - 1;
+    const uint64_t w = plk_poly_mul_workspace_bytes(la, lb);
+    if (w > mw) mw = w;
+  };
+  product(kq, p.m, true);   // q den
+  for (uint64_t t = p.B; t < p.k;) {
+    const uint64_t n2 = 2 * t < p.k ? 2 * t : p.k;
+    product(p.fl < n2 ? p.fl : n2, t, true);
+    product(t, n2 - t, false);
+    t = n2;
+  }
+  size_t o = up256(divide_base_bytes(nl, dl));
+  p.o_g = o, o += up256(2 * p.k);
+  p.o_ar = o, o += up256(p.k);
+  p.o_f = o, o += up256(p.fl);
+  p.o_p = o, o += up256(pout);
+  p.o_e = o, o += up256((p.k + 1) / 2);
+  p.o_mw = o, o += up256(mw);
+  p.total = o;
+  return p;
+}
+
+// covers the Newton buffers of every shape that could take that path, whatever
+// PLK_OPT_DIVIDE_FAST_MIN is now
+size_t plk_poly_divide_workspace_bytes(uint64_t nl, uint64_t dl) {
+  return newton_shape(nl, dl) ? newton_plan(nl, dl).total : divide_base_bytes(nl, dl);
+}
+
+// The divisor's class, from one pass over its (host) bytes.  path: 0 trivial (nl < dl), 1 constant,
+// 2 binomial scan, 3 the reference's loop on one thread, 4 Newton; a zero divisor or a lead byte
+// >= 17: the error code negated (the message is set).
+struct DivClass {
+  int path;
+  bool canonical_den, binom;   // every byte < 17; no non-zero byte between den[0] and the lead
+};
+static int divide_path(const uint8_t* den, uint64_t dl, uint64_t nl, bool any, bool canonical_den, bool binom) {
+  if (!any) {
+    plk_set_error("Division by zero polynomial in poly_divide");
+    return -PLK_ERR_ARG;
+  }
+  const uint32_t lead = den[dl - 1];
+  if (lead >= HP) {   // the reference indexes hf_inverses[17] out of bounds: undefined
+    plk_set_error("poly_divide: divisor lead byte %u is not a GF(17) value (reference behaviour undefined)", lead);
+    return -PLK_ERR_RANGE;
+  }
+  if (canonical_den && binom && lead != 0) return nl < dl ? 0 : (dl == 1 ? 1 : 2);
+  if (nl < dl) return 0;
+  const uint64_t fast = (uint64_t)plk_opt(PLK_OPT_DIVIDE_FAST_MIN);
+  const uint64_t ql = nl - dl + 1;
+  // (ql dl >= fast, without the product's overflow)
+  if (fast && canonical_den && lead != 0 && newton_shape(nl, dl) && dl >= (fast + ql - 1) / ql) return 4;
+  return 3;
+}
+static DivClass divide_classify(const uint8_t* den, uint64_t dl, uint64_t nl) {
+  // (plain OR reductions, which the host compiler vectorises: a 2^20-byte divisor is scanned per call)
+  uint8_t any = 0, big = 0, mid = 0;
+  for (uint64_t i = 0; den && i < dl; i++) {
+    any |= den[i];
+    big |= (uint8_t)(den[i] >= HP);
+  }
+  for (uint64_t i = 1; den && i + 1 < dl; i++) mid |= den[i];
+  DivClass c{0, !big, !mid};
+  c.path = divide_path(den, dl, nl, any != 0, c.canonical_den, c.binom);
+  return c;
+}
+int plk_poly_divide_classify(const uint8_t* den, uint64_t dl, uint64_t nl) { return divide_classify(den, dl, nl).path; }
+
+static unsigned chunk_blocks(uint64_t bytes) {
+  const uint64_t b = (((bytes + 15) >> 4) + 255) / 256;
+  return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+}
+
+// The Newton path's launches (d_den: the divisor's device copy, enqueued before): 2 glue kernels,
+// 3 launches per doubling step (two products and the negation), the two closing products with
+// their reversal / subtraction.  div_finish_kernel follows (trims; the loop when flagged).
+static int newton_divide(const uint8_t* d_num, uint64_t nl, const uint8_t* d_den, uint64_t dl, uint8_t* d_q,
+                         uint8_t* d_rem, uint32_t* flag, uint8_t* w, hipStream_t st) {
+  const NewtonPlan p = newton_plan(nl, dl);
+  uint8_t *G = w + p.o_g, *AR = w + p.o_ar, *F = w + p.o_f, *P = w + p.o_p, *E = w + p.o_e;
+  void* mw = w + p.o_mw;
+  int rc;
+  // a[0, k) = rev(num)[0, k) (checked), f[0, fl) = rev(den)[0, fl)
+  RevJobs J{{{d_num + p.m, AR, p.k, 1}, {d_den + (dl - p.fl), F, p.fl, 0}}, flag};
+  hipLaunchKernelGGL(div_reverse_kernel, dim3(chunk_blocks(p.k), 2), dim3(256), 0, st, J);
+  PLK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(div_base_inverse_kernel, dim3(1), dim3(INV_B0), 0, st, F, (uint32_t)(p.fl < INV_B0 ? p.fl : INV_B0),
+                     (uint32_t)p.B, G);
+  PLK_HIP(hipGetLastError());
+  for (uint64_t t = p.B; t < p.k;) {
+    const uint64_t n2 = 2 * t < p.k ? 2 * t : p.k, fl2 = p.fl < n2 ? p.fl : n2;
+    if ((rc = plk_poly_mul_launch(F, fl2, G, t, P, nullptr, mw, st))) return rc;
+    hipLaunchKernelGGL(div_newton_neg_kernel, dim3(chunk_blocks(n2 - t)), dim3(256), 0, st, P, fl2 + t - 1, t, E, n2 - t);
+    PLK_HIP(hipGetLastError());
+    if ((rc = plk_poly_mul_launch(G, t, E, n2 - t, G + t, nullptr, mw, st))) return rc;
+    t = n2;
+  }
+  // rev(q) = (a g)[0, k)
+  if ((rc = plk_poly_mul_launch(AR, p.k, G, p.k, P, nullptr, mw, st))) return rc;
+  RevJobs Q{{{P, d_q, p.k, 0}, {nullptr, nullptr, 0, 0}}, flag};
+  hipLaunchKernelGGL(div_reverse_kernel, dim3(chunk_blocks(p.k), 1), dim3(256), 0, st, Q);
+  PLK_HIP(hipGetLastError());
+  // rem = num - (q[0, min(k, m)) den[0, m))[0, m)
+  if ((rc = plk_poly_mul_launch(d_q, p.k < p.m ? p.k : p.m, d_den, p.m, P, nullptr, mw, st))) return rc;
+  hipLaunchKernelGGL(div_rem_sub_kernel, dim3(chunk_blocks(p.m)), dim3(256), 0, st, d_num, P, p.m, d_rem, flag);
+  PLK_HIP(hipGetLastError());
+  return PLK_OK;
+}
+
 // Classifies the divisor on the host (den is a host array; the kernels get its bytes by value or
 // in d_work), enqueues the division; d_lens[0] / d_lens[1] receive the index + 1 of the last
 // non-zero quotient / remainder byte (0 if none) over the untrimmed lengths
 // ql = nl >= dl ? nl - dl + 1 : 1 and rl = min(dl - 1, nl).
 int plk_poly_divide_launch(const uint8_t* d_num, uint64_t nl, const uint8_t* den, uint64_t dl, uint8_t* d_q,
                            uint8_t* d_rem, uint32_t* d_lens, void* d_work, hipStream_t st) {
-  if (!den || dl == 0) {
-    plk_set_error("Division by zero polynomial in poly_divide");
-    return PLK_ERR_ARG;
-  }
-  bool zero = true;
-  for (uint64_t i = 0; i < dl && zero; i++) zero = den[i] == 0;
-  if (zero) {
-    plk_set_error("Division by zero polynomial in poly_divide");
-    return PLK_ERR_ARG;
-  }
+  const DivClass cls = divide_classify(den, dl, nl);
+  const int path = cls.path;
+  if (path < 0) return -path;
   const uint32_t lead = den[dl - 1];
-  if (lead >= HP) {   // the reference indexes hf_inverses[17] out of bounds: undefined
-    plk_set_error("poly_divide: divisor lead byte %u is not a GF(17) value (reference behaviour undefined)", lead);
-    return PLK_ERR_RANGE;
-  }
   if (nl && !d_num) {
     plk_set_error("poly_divide: NULL numerator");
     return PLK_ERR_ARG;
@@ -485,20 +771,20 @@ int plk_poly_divide_launch(const uint8_t* d_num, uint64_t nl, const uint8_t* den
   uint32_t* flag = (uint32_t*)w;           // [0] non-canonical flag
   uint8_t* d_den = w + 256;
   uint32_t* bsum = (uint32_t*)(w + 256 + ((dl + 15) & ~15ull));
-  uint8_t* scratch = w + plk_poly_divide_workspace_bytes(nl, dl) - ((nl + 15) & ~15ull);   // last nl bytes
+  uint8_t* scratch = w + divide_base_bytes(nl, dl) - ((nl + 15) & ~15ull);   // the base part's last nl bytes
   PLK_HIP(hipMemsetAsync(flag, 0, 16, st));
-  bool canonical_den = true;
-  bool binom = true;
-  for (uint64_t i = 0; i < dl; i++) {
-    canonical_den &= den[i] < HP;
-    if (i > 0 && i + 1 < dl && den[i]) binom = false;
-  }
+  const bool canonical_den = cls.canonical_den, binom = cls.binom;
   const uint32_t inv = [](uint32_t a) {
     static const uint8_t t[17] = {0, 1, 9, 6, 13, 7, 3, 5, 15, 2, 12, 14, 10, 4, 11, 8, 16};
     return (uint32_t)t[a];
   }(lead);
-  bool serial = !canonical_den || !binom || lead == 0;
-  if (!serial) {
+  const bool newton = path == 4;
+  const bool serial = (!canonical_den || !binom || lead == 0) && !newton;
+  if (newton) {
+    PLK_HIP(hipMemcpyAsync(d_den, den, dl, hipMemcpyHostToDevice, st));
+    const int rc = newton_divide(d_num, nl, d_den, dl, d_q, d_rem, flag, w, st);
+    if (rc) return rc;
+  } else if (!serial) {
     if (nl < dl) {
       // no loop step: q = {0}, rem = num[0 .. rl) -- parallel path still checks num's bytes
       PLK_HIP(hipMemsetAsync(d_q, 0, 1, st));
@@ -532,9 +818,10 @@ int plk_poly_divide_launch(const uint8_t* d_num, uint64_t nl, const uint8_t* den
   }
   // a divisor outside the parallel forms, or (binomial path) non-canonical numerator bytes: the
   // reference's loop.  (m = 0 and nl < dl are exact for any bytes: hf_mul reduces, copies copy.)
+  // (Newton path: gated the same way, the loop reading the divisor's device copy)
   const bool gated = !serial && nl >= dl && m > 0;
   if (serial) PLK_HIP(hipMemcpyAsync(d_den, den, dl, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(div_finish_kernel, dim3(1), dim3(1024), 0, st, d_num, nl, serial ? d_den : nullptr, dl,
+  hipLaunchKernelGGL(div_finish_kernel, dim3(1), dim3(1024), 0, st, d_num, nl, serial || newton ? d_den : nullptr, dl,
                      (uint32_t)den[0], lead, d_q, ql, d_rem, rl, serial ? 1 : (gated ? 2 : 0), flag, scratch, d_lens);
   PLK_HIP(hipGetLastError());
   return PLK_OK;

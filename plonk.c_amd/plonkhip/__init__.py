@@ -59,6 +59,7 @@ SIGNATURES = {
     "plk_poly_eval_batch_dev": (C.c_int, [C.POINTER(_vp), C.POINTER(_sz), _u8p, C.c_int, _vp, _vp, _vp]),
     "plk_poly_divide": (C.c_int, [_u8p, _sz, _u8p, _sz, _u8p, C.POINTER(_sz), _u8p, C.POINTER(_sz)]),
     "plk_poly_divide_workspace": (_sz, [_sz, _sz]),
+    "plk_poly_divide_path": (C.c_int, [_u8p, _sz, _sz]),
     "plk_poly_divide_dev": (C.c_int, [_vp, _sz, _u8p, _sz, _vp, _vp, _vp, _vp, _vp]),
     "plk_matrix_mul": (C.c_int, [_u8p, _sz, _sz, _u8p, _sz, _u8p]),
     "plk_matrix_inv": (C.c_int, [_u8p, _sz, _u8p]),
@@ -96,7 +97,7 @@ OPTIONS = {"TINY_CALLS": 1, "PROVE_SYNC": 2, "POLY_BLOCK_L": 3, "POLY_BLOCK_S": 
            "PROVE_FUSE_DIV": 21, "PROVE_SRS_LOGS": 22,
            "PROVE_PACK_FUSE": 23, "PROVE_EARLY_COMMITS": 24,
            "PROVE_HELPER_COPY": 25, "PROVE_EVAL_AGG": 26, "PROVE_GRAPH": 27,
-           "DROPIN_HOST_WORK": 28}
+           "DROPIN_HOST_WORK": 28, "DIVIDE_FAST_MIN": 29}
 
 PLK_PROVE_STRICT = 1
 PLK_PROVE_PREPROCESSED = 2
@@ -434,6 +435,13 @@ def poly_eval_batch_dev(polys, lens, xs, ys, tick, stream=None):
 
 def poly_divide_workspace(nl, dl):
     return int(lib().plk_poly_divide_workspace(int(nl), int(dl)))
+
+
+def poly_divide_path(den, nl):
+    """plk_poly_divide_path: 0 trivial, 1 constant, 2 binomial scan, 3 serial loop, 4 Newton under the
+    current options; a negated PLK_ERR_* for a zero divisor / a lead byte >= 17.  No device needed."""
+    d = _u8(den).reshape(-1)
+    return int(lib().plk_poly_divide_path(_p(d), d.size, int(nl)))
 
 
 def poly_divide_dev(num, nl, den, quot, rem, lens, work, stream=None):
