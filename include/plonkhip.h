@@ -173,6 +173,12 @@ int plk_msm_g1_dev(const uint8_t *d_points, const uint8_t *d_scalars, size_t n,
 int plk_msm_g1_batch_dev(const uint8_t *d_points, size_t points_stride, const uint8_t *d_scalars,
                          size_t scalars_stride, size_t n, int batch, plk_msm_result_t *d_res,
                          void *stream);
+/* The launch plan plk_msm_g1_dev (batch = 1) / plk_msm_g1_batch_dev take for batch MSMs of n
+ * points under the current options; aligned = 0: some base or stride is not 16-byte aligned.
+ * out = {threads per block, blocks per MSM, groups in flight, table copies, half groups}.
+ * PLK_ERR_ARG for batch <= 0 or a NULL out, PLK_ERR_RANGE for batch > 65535 (as the launch).
+ * Host only: touches no device, works with no GPU present. */
+int plk_msm_plan(size_t n, int batch, int aligned, int out[5]);
 int plk_msm_g1_serial_dev(const uint8_t *d_points, const uint8_t *d_scalars, size_t n,
                           plk_msm_result_t *d_res, void *stream);
 /* out3 = EXP[(sum of count partial logs) mod 102] -- combines per-shard partials after a

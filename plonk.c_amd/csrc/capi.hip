@@ -809,6 +809,19 @@ int plk_msm_g1_batch_dev(const uint8_t* d_points, size_t points_stride, const ui
   return plk_msm_batch_launch(d_points, points_stride, d_scalars, scalars_stride, n, batch, d_res, pick(stream));
 }
 
+int plk_msm_plan(size_t n, int batch, int aligned, int out[5]) {
+  if (batch <= 0 || !out) {
+    plk_set_error("plk_msm_plan: batch %d, out %p", batch, (void*)out);
+    return PLK_ERR_ARG;
+  }
+  if (batch > 65535) {
+    plk_set_error("plk_msm batch %d too large", batch);
+    return PLK_ERR_RANGE;
+  }
+  plk_msm_launch_plan(n, batch, aligned != 0, &out[0], &out[1], &out[2], &out[3], &out[4]);
+  return PLK_OK;
+}
+
 int plk_msm_g1_serial_dev(const uint8_t* d_points, const uint8_t* d_scalars, size_t n, plk_msm_result_t* d_res,
                           void* stream) {
   int rc = ensure_dev();

@@ -972,11 +972,24 @@ void plk_msm_geometry(uint64_t n, int batch, int* threads, int* blocks, int* gpt
   if (half) *half = hf;
 }
 
+// The plan of one launch: plk_msm_geometry, and for the byte-wise form (some base or stride not
+// 16-byte aligned) the plain plan -- no half groups, one group in flight.  plk_msm_batch_launch
+// launches exactly this; plk_msm_plan (capi.hip) reports it.
+void plk_msm_launch_plan(uint64_t n, int batch, bool aligned, int* threads, int* blocks, int* gpt, int* copies,
+                         int* half) {
+  plk_msm_geometry(n, batch, threads, blocks, gpt, copies, half);
+  if (aligned) return;
+  if (*half) {
+    *half = 0;
+    *blocks /= 2;
+  }
+  *gpt = 1;
+}
+
 namespace {
 template <bool A, int T, int C>
 void go_g(int g, dim3 grid, hipStream_t st, const uint8_t* p, uint64_t ps, const uint8_t* s, uint64_t ss, uint64_t n,
           PlkMsmResult* r) {
-  if (!A) g = 1;
   const uint64_t span = (uint64_t)grid.x * T * g;
   const uint32_t full = (uint32_t)((n >> 4) / span);
   if (g == 1)
@@ -1010,13 +1023,9 @@ int plk_msm_batch_launch(const uint8_t* d_pts, uint64_t pstride, const uint8_t* 
     return PLK_ERR_RANGE;
   }
   int threads, blocks, g, c, half;
-  plk_msm_geometry(n, batch, &threads, &blocks, &g, &c, &half);
   const bool aligned = ((uintptr_t)d_pts % 16 == 0) && ((uintptr_t)d_sc % 16 == 0) &&
                        (batch == 1 || (pstride % 16 == 0 && sstride % 16 == 0));
-  if (!aligned && half) {   // the byte-wise form: the plain plan
-    half = 0;
-    blocks /= 2;
-  }
+  plk_msm_launch_plan(n, batch, aligned, &threads, &blocks, &g, &c, &half);
   const dim3 grid(blocks, batch);
   if (threads == 1024) go_t<1024>(aligned, g, c, half, grid, st, d_pts, pstride, d_sc, sstride, n, d_res);
   else if (threads == 512) go_t<512>(aligned, g, c, half, grid, st, d_pts, pstride, d_sc, sstride, n, d_res);

@@ -41,6 +41,7 @@ SIGNATURES = {
     "plk_msm_result_init": (C.c_int, [_vp, _vp]),
     "plk_msm_g1_dev": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "plk_msm_g1_batch_dev": (C.c_int, [_vp, _sz, _vp, _sz, _sz, C.c_int, _vp, _vp]),
+    "plk_msm_plan": (C.c_int, [_sz, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "plk_msm_g1_serial_dev": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "plk_msm_combine_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "plk_msm_finalize_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
@@ -368,6 +369,14 @@ def msm_g1_batch_dev(points, points_stride, scalars, scalars_stride, n, batch, r
     _check("plk_msm_g1_batch_dev", lib().plk_msm_g1_batch_dev(
         _ptr(points), int(points_stride), _ptr(scalars), int(scalars_stride), int(n), int(batch),
         _ptr(res), _stream(stream)))
+
+
+def msm_plan(n, batch, aligned=True):
+    """plk_msm_plan: the launch plan of msm_g1_dev (batch = 1) / msm_g1_batch_dev for batch MSMs of n
+    points under the current options (aligned=False: the byte-wise form).  No device needed."""
+    out = (C.c_int * 5)()
+    _check("plk_msm_plan", lib().plk_msm_plan(int(n), int(batch), 1 if aligned else 0, out))
+    return dict(zip(("threads", "blocks", "groups", "copies", "half"), list(out)))
 
 
 def msm_g1_serial_dev(points, scalars, n, res, stream=None):
