@@ -1,5 +1,6 @@
 """CPU side of the prover row: the restatement oracle/prove_ref.py reproduces every reference
-proof and rejection recorded in tests/golden/prove.json (so it can serve as the parity oracle
+proof and rejection recorded in tests/golden/prove.json and, on degenerate circuits, challenges,
+blinding and SRS lengths, in tests/golden/prove_edges.json (so it can serve as the parity oracle
 for the device prover at sizes the reference cannot run), and the ctypes mirrors of the
 prover structs match the C header layout."""
 import subprocess
@@ -12,7 +13,11 @@ from prove_ref import Prover, ProveError, poly_eval
 
 
 def _run(o, g, case):
-    key = "short" if case["srs_n"] == 4 else str(case["srs_mode"])
+    if "circuit" in case:   # prove_edges.json: the circuit by name, setups by 'srs_n/srs_mode'
+        case = dict(g["circuits"][case["circuit"]], **case)
+        key = "%d/%d" % (case["srs_n"], case["srs_mode"])
+    else:
+        key = "short" if case["srs_n"] == 4 else str(case["srs_mode"])
     s = {k: bytes.fromhex(v) for k, v in g["setups"][key].items()}
     pr = Prover(o, s["g1s"], 4, s["h"], s["k1_h"], s["k2_h"], s["h_pows_inv"], s["z_h"])
     gt, cp, w = case["gates"], case["copies"], case["wires"]
@@ -36,6 +41,26 @@ def test_restated_prover_rejects_like_reference(oracle):
                 _run(oracle, g, case)
         else:
             assert _run(oracle, g, case).hex() == case["proof"]
+
+
+def test_restated_prover_matches_reference_on_edges(oracle):
+    """tests/golden/prove_edges.json: four circuits (one with q_c != 0, one all zero) x challenges and
+    blinding scalars zeroed x SRS lengths 4..9 around the commitment lengths, recorded from the compiled
+    reference.  The restatement gives every proof and takes every exit, so it can be the device
+    prover's answer on degenerate inputs at sizes the reference cannot run."""
+    g = load_golden("prove_edges.json")
+    proofs, failures = g["proofs"], g["failures"]
+    total = len(proofs) + len(failures)
+    assert total >= 400 and 4 * len(proofs) >= total and 4 * len(failures) >= total
+    assert {c["circuit"] for c in proofs} == set(g["circuits"]) == {"toy", "zero", "constant", "addition"}
+    assert any(g["circuits"]["constant"]["gates"][16:20])          # q_c != 0
+    assert {c["srs_n"] for c in proofs + failures} == {3, 4, 5, 6, 8}
+    for case in proofs:
+        assert _run(oracle, g, case).hex() == case["proof"], case
+    for case in failures:
+        assert case["proof"] is None
+        with pytest.raises(ProveError):
+            _run(oracle, g, case)
 
 
 def test_setup_matches_plonk_new():
