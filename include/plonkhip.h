@@ -290,6 +290,59 @@ int plk_matrix_inv(const uint8_t *mat, size_t n, uint8_t *out);
  * poly_new; out holds n bytes. */
 int plk_interpolate(const uint8_t *h_pows_inv, const uint8_t *values, size_t n, uint8_t *out, size_t *out_len);
 
+/* ---- KZG over a resident SRS: commit and open, batched ----------------------------------
+ * The commitment (srs_eval_at_s, src/srs.h:53-68) and the opening the reference spells out twice per
+ * proof (src/plonk.h:606-621: y = p(z), q = (p - y) / (x - z), [q]) against an SRS that stays on the
+ * device.  plk_srs_create uploads len G1s (3 B each) to the current device -- which must be the
+ * library's primary device -- and keeps the G1 form and, when every encoding is a canonical group
+ * element, the log form (1 B per point) the fast path reads.  The handle is immutable after
+ * creation and holds the library context like a prover (plk_shutdown keeps the tables while one is
+ * alive); every call on it is made with the handle's device current (PLK_ERR_ARG otherwise).
+ *
+ * Semantics (the specification; job b of a batch of n, any n):
+ *   commit  = plk_msm_g1(srs[0 .. lens[b]), polys[b], lens[b]) exactly, for any coefficient byte
+ *             (g1_mul takes the raw byte).
+ *   open    = the composition  y = plk_poly_eval(p, len, z);
+ *             (q, q_len) = the quotient of plk_poly_divide(p, len, {(17 - z) % 17, 1}, 2);
+ *             proof = plk_msm_g1(srs, q, q_len)      (len == 1: q = {0}, proof = the identity).
+ * The fast path serves the canonical case, every coefficient < 17 and a regular SRS: a ragged batch
+ * of commitments is one launch; a batch of openings is two (per-chunk aggregates of the suffix scan,
+ * then quotient bytes in registers dotted with the SRS logs; one when every polynomial has at most
+ * 4096 coefficients), and the quotient is stored only where asked for.  Launches carry 32 jobs
+ * each; larger batches run in consecutive launches on the stream.
+ *   Host forms (synchronous): a job with a coefficient byte >= 17, and every job when
+ *   plk_srs_irregular, runs that composition itself, its commitment over the resident G1 form (the
+ *   dlog launch, then the raw serial fold when that says irregular, as plk_msm_g1 does).
+ *   _dev forms (asynchronous; d_polys / d_quots are HOST arrays of device pointers, lens and zs host
+ *   arrays): such a job is left with d_res[b].irregular > 0 and g1 invalid -- the convention of
+ *   plk_msm_g1_dev -- while its batch neighbours are unaffected.  d_ys[b] and the bytes at
+ *   d_quots[b] (max(len - 1, 1) of them, untrimmed) are exact whenever the coefficients are
+ *   canonical, whatever the SRS.  Records: zeroed once (plk_msm_result_init), then reusable.
+ *   d_work: plk_kzg_workspace(lens, n) bytes, no initialisation needed (every word read was written
+ *   by the same call); may be NULL when no polynomial has more than 4096 coefficients.  Calls on
+ *   different streams with distinct workspaces and records may run concurrently.
+ * Errors: a NULL handle or array, n <= 0, lens[b] == 0, zs[b] >= 17 or a call from another device
+ * are PLK_ERR_ARG (checked before any device query); commit with lens[b] > plk_srs_len and open with
+ * max(lens[b] - 1, 1) > plk_srs_len are PLK_ERR_RANGE on the lengths as given (the reference's
+ * "degree exceeds SRS size": its callers pass trimmed polynomials); plk_srs_create with no GPU is
+ * PLK_ERR_NODEV. */
+typedef struct plk_srs plk_srs_t;
+int plk_srs_create(const uint8_t *g1s, size_t len, plk_srs_t **out);
+void plk_srs_destroy(plk_srs_t *s);              /* NULL: no-op */
+size_t plk_srs_len(const plk_srs_t *s);          /* 0 for NULL */
+int plk_srs_irregular(const plk_srs_t *s);       /* 1: some encoding is not a canonical group element */
+int plk_kzg_commit_batch(const plk_srs_t *s, const uint8_t *const *polys, const size_t *lens, int n,
+                         uint8_t *out3 /* 3 n */);
+int plk_kzg_open_batch(const plk_srs_t *s, const uint8_t *const *polys, const size_t *lens,
+                       const uint8_t *zs, int n, uint8_t *ys /* n */, uint8_t *proofs3 /* 3 n */);
+size_t plk_kzg_workspace(const size_t *lens, int n);   /* host only, no device touched; 0 for bad arguments */
+int plk_kzg_commit_batch_dev(const plk_srs_t *s, const uint8_t *const *d_polys, const size_t *lens, int n,
+                             plk_msm_result_t *d_res, void *stream);
+int plk_kzg_open_batch_dev(const plk_srs_t *s, const uint8_t *const *d_polys, const size_t *lens,
+                           const uint8_t *zs, int n, uint8_t *d_ys, plk_msm_result_t *d_res,
+                           uint8_t *const *d_quots /* NULL, or per job NULL / max(len-1,1) bytes */,
+                           void *d_work, void *stream);
+
 /* ---- device-resident prover (replaces plonk_new / plonk_prove / plonk_free,
  * src/plonk.h:53-139, 223-656, 120-139) ---------------------------------------------------
  * plk_prover_create uploads the SRS and Z_H once (the PLONK struct of plonk_new); the

@@ -87,6 +87,16 @@ SIGNATURES = {
     "plk_prover_helpers": (C.c_int, [_vp]),
     "plk_prover_rounds_multi_dev": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _u8p, _u8p, C.c_int, _u8p]),
     "plk_ntt_launch_log": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
+    "plk_srs_create": (C.c_int, [_u8p, _sz, C.POINTER(_vp)]),
+    "plk_srs_destroy": (None, [_vp]),
+    "plk_srs_len": (_sz, [_vp]),
+    "plk_srs_irregular": (C.c_int, [_vp]),
+    "plk_kzg_commit_batch": (C.c_int, [_vp, C.POINTER(_u8p), C.POINTER(_sz), C.c_int, _u8p]),
+    "plk_kzg_open_batch": (C.c_int, [_vp, C.POINTER(_u8p), C.POINTER(_sz), _u8p, C.c_int, _u8p, _u8p]),
+    "plk_kzg_workspace": (_sz, [C.POINTER(_sz), C.c_int]),
+    "plk_kzg_commit_batch_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), C.c_int, _vp, _vp]),
+    "plk_kzg_open_batch_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _u8p, C.c_int, _vp, _vp,
+                                         C.POINTER(_vp), _vp, _vp]),
 }
 
 # PLK_OPT_* (include/plonkhip.h), by the name without the prefix
@@ -486,6 +496,103 @@ def parse_result(res_bytes):
     return {"log": int.from_bytes(b[MSM_LOG_OFFSET:MSM_LOG_OFFSET + 4], "little"),
             "irregular": int.from_bytes(b[MSM_IRREGULAR_OFFSET:MSM_IRREGULAR_OFFSET + 4], "little"),
             "g1": b[MSM_G1_OFFSET:MSM_G1_OFFSET + 3]}
+
+
+# ---------------------------------------------------------------- KZG over a resident SRS
+class Srs:
+    """plk_srs_t: an SRS resident on the device (G1 form and log form); `with Srs(g1s) as s: ...`"""
+
+    def __init__(self, g1s):
+        pts = _u8(g1s).reshape(-1)
+        if pts.size % 3:
+            raise ValueError("an SRS is n x 3 bytes")
+        self._h = _vp()
+        _check("plk_srs_create", lib().plk_srs_create(_p(pts), pts.size // 3, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().plk_srs_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __len__(self):
+        return int(lib().plk_srs_len(self._h))
+
+    @property
+    def irregular(self):
+        return bool(lib().plk_srs_irregular(self._h))
+
+
+def _srs_h(srs):
+    return srs._h if isinstance(srs, Srs) else srs
+
+
+def _host_polys(polys):
+    arrs = [_u8(p).reshape(-1) for p in polys]
+    n = len(arrs)
+    ptrs = (_u8p * max(n, 1))(*[_p(a) for a in arrs])
+    lens = (_sz * max(n, 1))(*[a.size for a in arrs])
+    return arrs, ptrs, lens, n
+
+
+def kzg_commit(srs, polys):
+    """plk_kzg_commit_batch: [3 bytes] per polynomial, = msm_g1(srs[:len(p)], p)"""
+    arrs, ptrs, lens, n = _host_polys(polys)
+    out = np.zeros(3 * max(n, 1), np.uint8)
+    _check("plk_kzg_commit_batch", lib().plk_kzg_commit_batch(_srs_h(srs), ptrs, lens, n, _p(out)))
+    return [bytes(out[3 * i:3 * i + 3]) for i in range(n)]
+
+
+def kzg_open(srs, polys, zs):
+    """plk_kzg_open_batch: ([y], [proof 3 bytes]) -- y = p(z) and the commitment of (p - y) / (x - z)"""
+    arrs, ptrs, lens, n = _host_polys(polys)
+    za = _u8(zs).reshape(-1)
+    if za.size != n:
+        raise ValueError("one z per polynomial")
+    ys = np.zeros(max(n, 1), np.uint8)
+    out = np.zeros(3 * max(n, 1), np.uint8)
+    _check("plk_kzg_open_batch", lib().plk_kzg_open_batch(_srs_h(srs), ptrs, lens, _p(za), n, _p(ys), _p(out)))
+    return [int(v) for v in ys[:n]], [bytes(out[3 * i:3 * i + 3]) for i in range(n)]
+
+
+def kzg_workspace(lens):
+    """plk_kzg_workspace: bytes of d_work for kzg_open_dev over these lengths.  No device needed."""
+    n = len(lens)
+    ls = (_sz * max(n, 1))(*[int(v) for v in lens])
+    return int(lib().plk_kzg_workspace(ls, n))
+
+
+def kzg_commit_dev(srs, polys, lens, res, stream=None):
+    """polys: device tensors (or raw pointers); res: n zeroed plk_msm_result_t records."""
+    n = len(polys)
+    ptrs = (_vp * max(n, 1))(*[_ptr(p) for p in polys])
+    ls = (_sz * max(n, 1))(*[int(v) for v in lens])
+    _check("plk_kzg_commit_batch_dev", lib().plk_kzg_commit_batch_dev(_srs_h(srs), ptrs, ls, n, _ptr(res),
+                                                                      _stream(stream)))
+
+
+def kzg_open_dev(srs, polys, lens, zs, ys, res, quots=None, work=None, stream=None):
+    """polys / quots: device tensors (or raw pointers; quots None, or None per job); ys: n device
+    bytes; res: n zeroed records; work: kzg_workspace(lens) device bytes."""
+    n = len(polys)
+    ptrs = (_vp * max(n, 1))(*[_ptr(p) for p in polys])
+    ls = (_sz * max(n, 1))(*[int(v) for v in lens])
+    za = _u8(zs).reshape(-1)
+    qs = None if quots is None else (_vp * max(n, 1))(*[_ptr(q) for q in quots])
+    _check("plk_kzg_open_batch_dev", lib().plk_kzg_open_batch_dev(_srs_h(srs), ptrs, ls, _p(za), n, _ptr(ys),
+                                                                  _ptr(res), qs, _ptr(work), _stream(stream)))
 
 
 # ---------------------------------------------------------------- device prover
