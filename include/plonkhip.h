@@ -381,6 +381,49 @@ int plk_prover_prove(plk_prover_t *p, const plk_circuit_t *circuit, const uint8_
  * Without PLK_PROVE_STRICT non-zero remainders are tolerated (synthetic inputs). */
 int plk_prover_rounds_dev(plk_prover_t *p, const uint8_t *const d_polys[13], const uint8_t chal[5],
                           const uint8_t rand9[9], int flags, uint8_t proof[34]);
+/* Many whole proofs in one call (throughput proving of small circuits: many witnesses of one
+ * circuit, many challenge or blinding draws).  Entry b of plk_prover_prove_batch is
+ * plk_prover_prove(p, circuit b, chal b, rand b), circuit b being the 14 n bytes
+ *   q_m q_l q_r q_o q_c (n each) | copy_a copy_b copy_c (2n each, (type, index) pairs) | a b c (n each);
+ * entry b of plk_prover_rounds_batch is plk_prover_rounds_dev on the 13 polynomials of entry b (in its
+ * order, each zero padded to n bytes, entries 13 n bytes apart) with `flags` (PLK_PROVE_STRICT only;
+ * PLK_PROVE_PREPROCESSED is PLK_ERR_ARG).  An accepted entry gets the same 34 bytes and status 0; a
+ * rejected one 34 zero bytes and the status word below: the exit the single call would take, in its
+ * order.  One deliberate difference: a rounds_batch entry with a polynomial byte >= 17 takes the
+ * exit INPUT (PLK_ERR_ARG); its neighbours are unaffected.  The return value covers the call only:
+ * PLK_OK means every entry was processed, whatever the statuses.
+ *   per-entry status word: 0 = proof written; else
+ *     bits 0-7   the PLK_ERR_* code the single call would return,
+ *     bits 8-15  the exit: 1 GATE, 2 COPY, 3 SRS, 4 ACC, 5 REM_T, 6 SLICE, 7 REM_W1, 8 REM_W2, 9 INPUT,
+ *     bits 16-31 the gate index for GATE (the %u of "Constraint %u not satisfied.")
+ * Fused path (plk_prover_batch_path = 1): n <= PLK_PROVE_BATCH_MAX_N, a regular SRS (the prover's log
+ * form exists) and a canonical trimmed Z_H of length 2..n + 1: ONE kernel launch proves the whole
+ * batch, one wave per proof.  Otherwise (path 0) the host forms run the composition itself, one
+ * single call per entry, status and message from that call's return; the _dev forms (DEVICE arrays,
+ * asynchronous on `stream`, the fused path only) return PLK_ERR_RANGE.  The host forms stage through
+ * buffers owned by the prover, grown on demand and counted in plk_prover_device_bytes.
+ * Errors (checked before any device query): NULL arrays, batch <= 0 (PLK_ERR_ARG), batch > 1 << 24
+ * (PLK_ERR_RANGE), the circuit form on a prover created without tables, a call from another device
+ * (PLK_ERR_ARG).  One call at a time per prover; attached helpers are ignored. */
+#define PLK_PROVE_BATCH_MAX_N 16
+/* the text plk_last_error() holds after the single call that takes this exit, NUL-terminated and
+ * truncated to cap bytes; returns its full length (0 for status 0), -PLK_ERR_ARG for an unknown exit.
+ * Host only, no device. */
+int plk_prove_exit_message(uint32_t status, char *buf, size_t cap);
+/* 1 fused kernel, 0 composition, -PLK_ERR_* (NULL prover; circuit != 0 without tables); host only */
+int plk_prover_batch_path(const plk_prover_t *p, int circuit);
+int plk_prover_prove_batch(plk_prover_t *p, const uint8_t *circuits /* batch x 14n */,
+                           const uint8_t *chals /* 5 each */, const uint8_t *rands /* 9 each */, int batch,
+                           uint8_t *proofs /* 34 each */, uint32_t *status);
+int plk_prover_rounds_batch(plk_prover_t *p, const uint8_t *polys /* batch x 13 x n */, const uint8_t *chals,
+                            const uint8_t *rands, int flags, int batch, uint8_t *proofs, uint32_t *status);
+int plk_prover_prove_batch_dev(plk_prover_t *p, const uint8_t *d_circuits, const uint8_t *d_chals,
+                               const uint8_t *d_rands, int batch, uint8_t *d_proofs, uint32_t *d_status,
+                               void *stream);
+int plk_prover_rounds_batch_dev(plk_prover_t *p, const uint8_t *d_polys, const uint8_t *d_chals,
+                                const uint8_t *d_rands, int flags, int batch, uint8_t *d_proofs,
+                                uint32_t *d_status, void *stream);
+
 /* Preprocessed circuit (PLONK's preprocessed input; the reference re-derives it inside every
  * plonk_prove, src/plonk.h:386-503): the forward transforms round 3 needs of the fixed circuit
  * polynomials q_o q_m q_l q_r s_sigma_3 l_1_x (d_polys indices 3 4 5 6 10 12, device-resident,

@@ -195,5 +195,22 @@ int plk_poly_divide_launch(const uint8_t* d_num, uint64_t nl, const uint8_t* den
 int plk_matrix_mul_launch(const uint8_t* d_a, uint64_t m, uint64_t k, const uint8_t* d_b, uint64_t n, uint8_t* d_out,
                           hipStream_t st);
 int plk_matrix_inv_launch(const uint8_t* d_mat, uint64_t n, uint8_t* d_aug, uint8_t* d_out, hipStream_t st);
+// prove_batch.hip: a batch of whole proofs at n <= PLK_PROVE_BATCH_MAX_N in one launch (one wave per
+// proof).  Every pointer is device memory on the current device; `in` holds batch entries of 14 n
+// circuit bytes (circuit = 1: strict, the circuit checks on; h3 and hinv are then read) or of 13 x n
+// polynomial bytes (circuit = 0).  zh: the trimmed canonical Z_H (2 <= lz <= n + 1, lead in 1..16),
+// srs_log: the regular SRS in log form.  Per entry 34 proof bytes (zero when rejected) and a status
+// word as plonkhip.h describes it.  PLK_ERR_RANGE for a shape outside those bounds.
+struct PlkProveBatch {
+  const uint8_t *in, *chals, *rands;
+  uint8_t* proofs;
+  uint32_t* status;
+  const uint8_t *h3, *hinv, *zh, *srs_log;
+  const uint32_t* exp_words;
+  uint64_t srs_len;
+  uint32_t n, lz, batch, circuit, strict;
+};
+int plk_prove_batch_launch(const PlkProveBatch* a, hipStream_t st);
+
 // ntt.hip: index + 1 of the last non-zero byte of d[0, len) (0 if none) into *d_nz
 int plk_trim_launch(const uint8_t* d, uint64_t len, uint32_t* d_nz, hipStream_t st);

@@ -69,8 +69,8 @@ enum Stat : int {
   ST_REM_T = 10,        // t(x) numerator mod Z_H != 0
   ST_REM_W1 = 11,       // w_z remainder != 0
   ST_REM_W2 = 12,       // w_z_omega remainder != 0
-  ST_GATE = 13,         // 1 + first unsatisfied gate
-  ST_COPY = 14,         // 1 + first invalid copy constraint
+  ST_GATE = 13,         // ~(first unsatisfied gate); 0: none (the words start at 0: atomicMax, lowest index wins)
+  ST_COPY = 14,         // ~(first invalid copy constraint); 0: none
   ST_ACC = 15,          // acc_x(omega^n) (must be 1)
   NSTAT = 16
 };
@@ -1558,7 +1558,7 @@ __global__ void circuit_check_kernel(const uint8_t* __restrict__ cir, uint64_t n
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t a = wa[i], b = wb[i], c = wc[i];
     const uint32_t lhs = (ql[i] * a + qr[i] * b + qo[i] * c + qm[i] * (a * b % HFP) + qc[i]) % HFP;
-    if (lhs) atomicMin(&stat[ST_GATE], (uint32_t)i + 1);
+    if (lhs) atomicMax(&stat[ST_GATE], ~(uint32_t)i);
     vals[0 * n + i] = (uint8_t)a;
     vals[1 * n + i] = (uint8_t)b;
     vals[2 * n + i] = (uint8_t)c;
@@ -1570,7 +1570,7 @@ __global__ void circuit_check_kernel(const uint8_t* __restrict__ cir, uint64_t n
     for (int k = 0; k < 3; k++) {
       const uint32_t type = cp[2 * (k * n + i)], idx = cp[2 * (k * n + i) + 1];
       uint8_t s = 0;
-      if (type > 2 || idx == 0 || idx > n) atomicMin(&stat[ST_COPY], (uint32_t)(k * n + i) + 1);
+      if (type > 2 || idx == 0 || idx > n) atomicMax(&stat[ST_COPY], ~(uint32_t)(k * n + i));
       else s = h3[type * n + (idx - 1)];   // h | k1_h | k2_h
       vals[(8 + k) * n + i] = s;
     }
@@ -1734,6 +1734,12 @@ struct plk_prover {
   // batches ([1]-[2], [3]-[4]: every NTT pass kernel of the proof), recorded only while tev_on
   hipEvent_t tev[6] = {};
   bool tev_on = false;
+  // plk_prover_prove_batch / plk_prover_rounds_batch: Z_H's bytes are all < 17 (with n, zh_len and a
+  // regular SRS: the fused kernel's eligibility), and the host forms' staging buffer (status words,
+  // proofs, inputs, challenges, blinding; grown on demand, counted in plk_prover_device_bytes)
+  bool zh_canonical = false;
+  uint8_t* bt_mem = nullptr;
+  size_t bt_bytes = 0;
 };
 
 namespace {
@@ -2135,6 +2141,8 @@ int create_on(const plk_plonk_desc_t* d, int dev, plk_prover_t** out) {
   for (size_t i = 1; i + 1 < zl; i++)
     if (d->z_h[i] % HFP) P->zh_kind = 1;
   P->have_circuit_tables = d->h && d->k1_h && d->k2_h && d->h_pows_inv;
+  P->zh_canonical = true;
+  for (size_t i = 0; i < zl; i++) P->zh_canonical = P->zh_canonical && d->z_h[i] < HFP;
 
   const Lens L = lens_for(P->n, P->zh_len);
   const uint64_t n = P->n;
@@ -2260,6 +2268,7 @@ void plk_prover_destroy(plk_prover_t* P) {
   if (P->st) (void)hipStreamSynchronize(P->st);
   drop_graph(P);
   (void)hipFree(P->mem);
+  (void)hipFree(P->bt_mem);
   if (P->h_res) (void)hipHostFree(P->h_res);
   (void)hipFree(P->fix_mem);
   (void)hipFree(P->hin);
@@ -2270,7 +2279,7 @@ void plk_prover_destroy(plk_prover_t* P) {
   plk_ctx_release();
 }
 
-size_t plk_prover_device_bytes(const plk_prover_t* P) { return P ? P->mem_bytes : 0; }
+size_t plk_prover_device_bytes(const plk_prover_t* P) { return P ? P->mem_bytes + P->bt_bytes : 0; }
 
 }  // extern "C"
 
@@ -2664,7 +2673,7 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
 // the reference's exits, in the order plonk_prove would hit them
 int check_status(const plk_prover* P, const uint32_t* st, int strict, int circuit) {
   const uint64_t part = P->n + 2;
-  if (circuit && st[ST_GATE]) { plk_set_error("Constraint %u not satisfied.", st[ST_GATE] - 1); return PLK_ERR_ARG; }
+  if (circuit && st[ST_GATE]) { plk_set_error("Constraint %u not satisfied.", ~st[ST_GATE]); return PLK_ERR_ARG; }
   if (circuit && st[ST_COPY]) { plk_set_error("Invalid copy_of type"); return PLK_ERR_ARG; }
   for (int i = 0; i < 3; i++)
     if (st[ST_LEN0 + i] > P->srs_len) { plk_set_error("SRS length is less than polynomial length"); return PLK_ERR_RANGE; }
@@ -3296,6 +3305,214 @@ int plk_prover_prove(plk_prover_t* P, const plk_circuit_t* c, const uint8_t chal
   int rc = P->nhelp ? rounds_split(P, pl, nullptr, chal, rand9, false) : rounds(P, pl, chal, rand9);
   if (rc) { (void)hipStreamSynchronize(P->st); return rc; }
   return finish(P, 1, 1, proof);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ batches of whole proofs
+namespace {
+
+// the exits of check_status by their number in a batch status word (plonkhip.h), with the text
+// check_status sets and the code it returns
+enum { X_GATE = 1, X_COPY, X_SRS, X_ACC, X_REM_T, X_SLICE, X_REM_W1, X_REM_W2, X_INPUT, X_COUNT };
+const struct { const char* msg; int code; } EXITS[X_COUNT] = {
+    {"", PLK_OK},
+    {"Constraint %u not satisfied.", PLK_ERR_ARG},
+    {"Invalid copy_of type", PLK_ERR_ARG},
+    {"SRS length is less than polynomial length", PLK_ERR_RANGE},
+    {"assertion acc_x(omega^n) == 1 failed", PLK_ERR_ARG},
+    {"Non-zero remainder in t(x) division", PLK_ERR_ARG},
+    {"Invalid slice indices in poly_slice", PLK_ERR_RANGE},
+    {"assertion poly_is_zero(&rem1) failed", PLK_ERR_ARG},
+    {"assertion poly_is_zero(&rem2) failed", PLK_ERR_ARG},
+    {"polynomial byte >= 17 in a batch entry", PLK_ERR_ARG}};
+
+// the status word of a single call that returned rc with this plk_last_error() text; 0 when the text
+// is none of check_status's (the call itself failed)
+uint32_t status_of_error(int rc, const char* msg) {
+  unsigned gate = 0;
+  if (sscanf(msg, "Constraint %u not satisfied.", &gate) == 1)
+    return (uint32_t)EXITS[X_GATE].code | (X_GATE << 8) | ((uint32_t)gate << 16);
+  for (int k = X_COPY; k < X_INPUT; k++)
+    if (!strcmp(msg, EXITS[k].msg) && rc == EXITS[k].code) return (uint32_t)rc | ((uint32_t)k << 8);
+  return 0;
+}
+
+bool batch_fused(const plk_prover* P) {
+  return P->n <= PLK_PROVE_BATCH_MAX_N && !P->srs_irregular && P->zh_canonical && P->zh_len >= 2 &&
+         P->zh_len <= P->n + 1;
+}
+
+// the argument checks of the four entry points, before any device query
+int batch_args(const char* fn, const plk_prover* P, const void* in, const void* chals, const void* rands, int flags,
+               int batch, const void* proofs, const void* status, bool circuit) {
+  if (!P || !in || !chals || !rands || !proofs || !status) { plk_set_error("%s: NULL argument", fn); return PLK_ERR_ARG; }
+  if (batch <= 0) { plk_set_error("%s: batch = %d", fn, batch); return PLK_ERR_ARG; }
+  if (batch > (1 << 24)) { plk_set_error("%s: batch = %d exceeds 2^24", fn, batch); return PLK_ERR_RANGE; }
+  if (flags & ~PLK_PROVE_STRICT) { plk_set_error("%s: flags other than PLK_PROVE_STRICT", fn); return PLK_ERR_ARG; }
+  if (circuit && !P->have_circuit_tables) {
+    plk_set_error("%s: prover created without h / k1_h / k2_h / h_pows_inv", fn);
+    return PLK_ERR_ARG;
+  }
+  if (plk_cur_device() != P->dev) {
+    plk_set_error("%s: the prover lives on device %d but the calling thread's current device is %d", fn, P->dev,
+                  plk_cur_device());
+    return PLK_ERR_ARG;
+  }
+  return PLK_OK;
+}
+
+int batch_launch(const plk_prover* P, const uint8_t* in, const uint8_t* chals, const uint8_t* rands, int strict, int batch,
+                 uint8_t* proofs, uint32_t* status, bool circuit, hipStream_t st) {
+  if (!batch_fused(P)) {
+    plk_set_error("prover not eligible for the fused batch kernel");
+    return PLK_ERR_RANGE;
+  }
+  const PlkProveBatch a{in, chals, rands, proofs, status, P->d_h3, P->d_hinv, P->d_zh, P->d_srs_log, P->exp_words,
+                        (uint64_t)P->srs_len, (uint32_t)P->n, (uint32_t)P->zh_len, (uint32_t)batch, circuit ? 1u : 0u,
+                        strict ? 1u : 0u};
+  return plk_prove_batch_launch(&a, st);
+}
+
+// host form, fused: stage in, one launch, stage out
+int batch_host_fused(plk_prover* P, const uint8_t* in, size_t in_each, const uint8_t* chals, const uint8_t* rands, int strict,
+                     int batch, uint8_t* proofs, uint32_t* status, bool circuit) {
+  const size_t b = (size_t)batch;
+  const size_t o_st = 0, o_pr = 4 * b, o_in = o_pr + ((34 * b + 15) & ~(size_t)15),
+               o_ch = o_in + ((in_each * b + 15) & ~(size_t)15), o_rd = o_ch + ((5 * b + 15) & ~(size_t)15),
+               need = o_rd + 9 * b;
+  if (need > P->bt_bytes) {
+    PLK_HIP(hipStreamSynchronize(P->st));
+    (void)hipFree(P->bt_mem);
+    P->bt_mem = nullptr;
+    P->bt_bytes = 0;
+    if (hipMalloc((void**)&P->bt_mem, need) != hipSuccess) {
+      P->bt_mem = nullptr;
+      plk_set_error("prover batch: hipMalloc(%zu) failed", need);
+      return PLK_ERR_NOMEM;
+    }
+    P->bt_bytes = need;
+  }
+  uint8_t* m = P->bt_mem;
+  PLK_HIP(hipMemcpyAsync(m + o_in, in, in_each * b, hipMemcpyHostToDevice, P->st));
+  PLK_HIP(hipMemcpyAsync(m + o_ch, chals, 5 * b, hipMemcpyHostToDevice, P->st));
+  PLK_HIP(hipMemcpyAsync(m + o_rd, rands, 9 * b, hipMemcpyHostToDevice, P->st));
+  const int rc = batch_launch(P, m + o_in, m + o_ch, m + o_rd, strict, batch, m + o_pr, (uint32_t*)(m + o_st), circuit, P->st);
+  if (rc) { (void)hipStreamSynchronize(P->st); return rc; }
+  PLK_HIP(hipMemcpyAsync(proofs, m + o_pr, 34 * b, hipMemcpyDeviceToHost, P->st));
+  PLK_HIP(hipMemcpyAsync(status, m + o_st, 4 * b, hipMemcpyDeviceToHost, P->st));
+  PLK_HIP(hipStreamSynchronize(P->st));
+  return PLK_OK;
+}
+
+// one entry's outcome from its single call's return: a reference exit becomes its status word
+int batch_entry_done(int rc, uint8_t* proof, uint32_t* status) {
+  *status = 0;
+  if (!rc) return PLK_OK;
+  memset(proof, 0, 34);
+  *status = status_of_error(rc, plk_last_error());
+  return *status ? PLK_OK : rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int plk_prove_exit_message(uint32_t status, char* buf, size_t cap) {
+  const uint32_t kind = (status >> 8) & 0xFFu;
+  char text[96];
+  int len = 0;
+  text[0] = 0;
+  if (status) {
+    if (kind == 0 || kind >= X_COUNT) return -PLK_ERR_ARG;
+    len = kind == X_GATE ? snprintf(text, sizeof text, EXITS[X_GATE].msg, (unsigned)(status >> 16))
+                         : snprintf(text, sizeof text, "%s", EXITS[kind].msg);
+  }
+  if (buf && cap) snprintf(buf, cap, "%s", text);
+  return len;
+}
+
+int plk_prover_batch_path(const plk_prover_t* P, int circuit) {
+  if (!P) { plk_set_error("plk_prover_batch_path: NULL prover"); return -PLK_ERR_ARG; }
+  if (circuit && !P->have_circuit_tables) {
+    plk_set_error("plk_prover_batch_path: prover created without h / k1_h / k2_h / h_pows_inv");
+    return -PLK_ERR_ARG;
+  }
+  return batch_fused(P) ? 1 : 0;
+}
+
+int plk_prover_prove_batch(plk_prover_t* P, const uint8_t* circuits, const uint8_t* chals, const uint8_t* rands,
+                           int batch, uint8_t* proofs, uint32_t* status) {
+  int rc = batch_args("plk_prover_prove_batch", P, circuits, chals, rands, 0, batch, proofs, status, true);
+  if (rc) return rc;
+  const size_t n = P->n;
+  if (batch_fused(P)) return batch_host_fused(P, circuits, 14 * n, chals, rands, 1, batch, proofs, status, true);
+  const int nhelp = P->nhelp;
+  P->nhelp = 0;   // (attached helpers are ignored)
+  for (int b = 0; b < batch && !rc; b++) {
+    const uint8_t* c = circuits + (size_t)b * 14 * n;
+    const plk_circuit_t cir{c, c + n, c + 2 * n, c + 3 * n, c + 4 * n, c + 5 * n, c + 7 * n, c + 9 * n,
+                            c + 11 * n, c + 12 * n, c + 13 * n};
+    rc = batch_entry_done(plk_prover_prove(P, &cir, chals + 5 * (size_t)b, rands + 9 * (size_t)b, proofs + 34 * (size_t)b),
+                          proofs + 34 * (size_t)b, status + b);
+  }
+  P->nhelp = nhelp;
+  return rc;
+}
+
+int plk_prover_rounds_batch(plk_prover_t* P, const uint8_t* polys, const uint8_t* chals, const uint8_t* rands, int flags,
+                            int batch, uint8_t* proofs, uint32_t* status) {
+  int rc = batch_args("plk_prover_rounds_batch", P, polys, chals, rands, flags, batch, proofs, status, false);
+  if (rc) return rc;
+  const size_t n = P->n;
+  if (batch_fused(P)) return batch_host_fused(P, polys, 13 * n, chals, rands, flags & PLK_PROVE_STRICT, batch, proofs, status, false);
+  // the composition: each entry's 13 polynomials staged at 16-byte aligned rows, then the single call
+  const size_t row = (n + 15) & ~(size_t)15;
+  uint8_t* d = nullptr;
+  if (hipMalloc((void**)&d, 13 * row + 16) != hipSuccess) {
+    plk_set_error("plk_prover_rounds_batch: hipMalloc(%zu) failed", 13 * row + 16);
+    return PLK_ERR_NOMEM;
+  }
+  const int nhelp = P->nhelp;
+  P->nhelp = 0;   // (attached helpers are ignored)
+  const uint8_t* pl[13];
+  for (int i = 0; i < 13; i++) pl[i] = d + (size_t)i * row;
+  for (int b = 0; b < batch && !rc; b++) {
+    const uint8_t* src = polys + (size_t)b * 13 * n;
+    uint8_t* const proof = proofs + 34 * (size_t)b;
+    bool big = false;
+    for (size_t i = 0; i < 13 * n; i++) big = big || src[i] >= HFP;
+    if (big) {
+      memset(proof, 0, 34);
+      status[b] = (uint32_t)PLK_ERR_ARG | (X_INPUT << 8);
+      continue;
+    }
+    if (hipMemcpy2D(d, row, src, n, n, 13, hipMemcpyHostToDevice) != hipSuccess) {
+      plk_set_error("plk_prover_rounds_batch: staging copy failed");
+      rc = PLK_ERR_HIP;
+      break;
+    }
+    rc = batch_entry_done(plk_prover_rounds_dev(P, pl, chals + 5 * (size_t)b, rands + 9 * (size_t)b, flags, proof), proof,
+                          status + b);
+  }
+  P->nhelp = nhelp;
+  (void)hipFree(d);
+  return rc;
+}
+
+int plk_prover_prove_batch_dev(plk_prover_t* P, const uint8_t* d_circuits, const uint8_t* d_chals, const uint8_t* d_rands,
+                               int batch, uint8_t* d_proofs, uint32_t* d_status, void* stream) {
+  const int rc = batch_args("plk_prover_prove_batch_dev", P, d_circuits, d_chals, d_rands, 0, batch, d_proofs, d_status, true);
+  if (rc) return rc;
+  return batch_launch(P, d_circuits, d_chals, d_rands, 1, batch, d_proofs, d_status, true, (hipStream_t)stream);
+}
+
+int plk_prover_rounds_batch_dev(plk_prover_t* P, const uint8_t* d_polys, const uint8_t* d_chals, const uint8_t* d_rands,
+                                int flags, int batch, uint8_t* d_proofs, uint32_t* d_status, void* stream) {
+  const int rc = batch_args("plk_prover_rounds_batch_dev", P, d_polys, d_chals, d_rands, flags, batch, d_proofs, d_status, false);
+  if (rc) return rc;
+  return batch_launch(P, d_polys, d_chals, d_rands, flags & PLK_PROVE_STRICT, batch, d_proofs, d_status, false,
+                      (hipStream_t)stream);
 }
 
 }  // extern "C"

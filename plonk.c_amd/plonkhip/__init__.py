@@ -73,6 +73,12 @@ SIGNATURES = {
     "plk_prover_profile_dev": (C.c_int, [_vp, C.POINTER(_vp), _u8p, _u8p, C.c_int, _u8p, C.POINTER(C.c_double)]),
     "plk_prover_launches": (C.c_int, [_vp, C.POINTER(_vp), _u8p, _u8p, C.c_int, C.POINTER(C.c_int),
                                       C.POINTER(C.c_int)]),
+    "plk_prove_exit_message": (C.c_int, [C.c_uint32, C.c_char_p, _sz]),
+    "plk_prover_batch_path": (C.c_int, [_vp, C.c_int]),
+    "plk_prover_prove_batch": (C.c_int, [_vp, _u8p, _u8p, _u8p, C.c_int, _u8p, C.POINTER(C.c_uint32)]),
+    "plk_prover_rounds_batch": (C.c_int, [_vp, _u8p, _u8p, _u8p, C.c_int, C.c_int, _u8p, C.POINTER(C.c_uint32)]),
+    "plk_prover_prove_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "plk_prover_rounds_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "plk_prover_alg_bytes": (C.c_uint64, [_vp]),
     "plk_prover_preprocess": (C.c_int, [_vp, C.POINTER(_vp)]),
     "plk_prover_chain_bytes": (_sz, [_vp, C.c_int]),
@@ -596,6 +602,16 @@ def kzg_open_dev(srs, polys, lens, zs, ys, res, quots=None, work=None, stream=No
 
 
 # ---------------------------------------------------------------- device prover
+def prove_exit_message(status):
+    """the text of a batch entry's status word: what plk_last_error() holds after the single call
+    that takes the same exit ('' for 0)"""
+    buf = C.create_string_buffer(96)
+    rc = lib().plk_prove_exit_message(int(status), buf, len(buf))
+    if rc < 0:
+        raise ValueError("prove_exit_message: unknown exit in status word 0x%x" % int(status))
+    return buf.value.decode()
+
+
 class Prover:
     """plk_prover_t: plonk_new's setup on the device (SRS + Z_H [+ circuit tables]),
     plonk_prove as `prove` (circuit) or `rounds_dev` (device-resident interpolated polys)."""
@@ -632,6 +648,66 @@ class Prover:
         out = np.zeros(34, np.uint8)
         _check("plk_prover_prove", lib().plk_prover_prove(self._h, C.byref(cir), _p(ch), _p(rd), _p(out)))
         return bytes(out)
+
+    # -- many whole proofs per call (plk_prover_prove_batch / plk_prover_rounds_batch)
+    def batch_path(self, circuit=True):
+        """1: the fused kernel (one launch for the whole batch), 0: one single call per entry"""
+        rc = lib().plk_prover_batch_path(self._h, 1 if circuit else 0)
+        if rc < 0:
+            raise PlonkHipError("plk_prover_batch_path", -rc, last_error())
+        return rc
+
+    def _batch_host(self, fn, what, each, data, chals, rands):
+        d, ch, rd = _u8(data).reshape(-1), _u8(chals).reshape(-1), _u8(rands).reshape(-1)
+        batch = ch.size // 5
+        if batch == 0 or ch.size != 5 * batch:
+            raise ValueError("%s: chals must hold 5 values per entry (got %d)" % (fn, ch.size))
+        if rd.size != 9 * batch:
+            raise ValueError("%s: rands must hold 9 values per entry (%d entries, got %d)" % (fn, batch, rd.size))
+        if d.size != each * batch:
+            raise ValueError("%s: %s must hold %d bytes per entry (%d entries, got %d)" % (fn, what, each, batch, d.size))
+        return d, ch, rd, batch, np.zeros(34 * batch, np.uint8), np.zeros(batch, np.uint32)
+
+    def prove_batch(self, circuits, chals, rands):
+        """circuits: batch x 14n bytes (q_m q_l q_r q_o q_c | copy_a copy_b copy_c | a b c per entry);
+        returns (34 * batch proof bytes, uint32 status per entry: 0 or prove_exit_message's word)"""
+        d, ch, rd, batch, out, st = self._batch_host("prove_batch", "circuits", 14 * self.n, circuits, chals, rands)
+        _check("plk_prover_prove_batch", lib().plk_prover_prove_batch(
+            self._h, _p(d), _p(ch), _p(rd), batch, _p(out), st.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out.tobytes(), st
+
+    def rounds_batch(self, polys, chals, rands, strict=False):
+        """polys: batch x 13 x n bytes (rounds_dev's order, zero padded to n); returns as prove_batch"""
+        d, ch, rd, batch, out, st = self._batch_host("rounds_batch", "polys", 13 * self.n, polys, chals, rands)
+        _check("plk_prover_rounds_batch", lib().plk_prover_rounds_batch(
+            self._h, _p(d), _p(ch), _p(rd), PLK_PROVE_STRICT if strict else 0, batch, _p(out),
+            st.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out.tobytes(), st
+
+    def _batch_dev(self, fn, batch, sizes):
+        if batch <= 0:
+            raise ValueError("%s: batch = %d" % (fn, batch))
+        for (name, t, per) in sizes:
+            if hasattr(t, "numel") and t.numel() * t.element_size() < per * batch:
+                raise ValueError("%s: %s holds %d bytes, %d entries need %d" % (fn, name, t.numel() * t.element_size(),
+                                                                             batch, per * batch))
+
+    def prove_batch_dev(self, circuits, chals, rands, batch, proofs, status, stream=None):
+        """device tensors / pointers: circuits 14n, chals 5, rands 9, proofs 34 bytes per entry, status one
+        uint32 each; asynchronous on `stream`, the fused path only"""
+        self._batch_dev("prove_batch_dev", batch, (("circuits", circuits, 14 * self.n), ("chals", chals, 5),
+                                                               ("rands", rands, 9), ("proofs", proofs, 34),
+                                                               ("status", status, 4)))
+        _check("plk_prover_prove_batch_dev", lib().plk_prover_prove_batch_dev(
+            self._h, _ptr(circuits), _ptr(chals), _ptr(rands), batch, _ptr(proofs), _ptr(status), _stream(stream)))
+
+    def rounds_batch_dev(self, polys, chals, rands, batch, proofs, status, strict=False, stream=None):
+        self._batch_dev("rounds_batch_dev", batch, (("polys", polys, 13 * self.n), ("chals", chals, 5),
+                                                                ("rands", rands, 9), ("proofs", proofs, 34),
+                                                                ("status", status, 4)))
+        _check("plk_prover_rounds_batch_dev", lib().plk_prover_rounds_batch_dev(
+            self._h, _ptr(polys), _ptr(chals), _ptr(rands), PLK_PROVE_STRICT if strict else 0, batch, _ptr(proofs),
+            _ptr(status), _stream(stream)))
 
     def _args(self, polys, chal, rand):
         """ctypes argument blocks of (polys, chal, rand), cached by value"""
