@@ -104,10 +104,6 @@ enum {
   PLK_OPT_PROVE_EVAL_AGG = 26,   /* 1: round 4's evaluation rows also store round 5's scan-chunk aggregates, so
                                     both round-5 divisions finish in ONE launch (lincomb_agg_divide_kernel);
                                     0: the numerators + aggregates launch, then the apply launch */
-  PLK_OPT_PROVE_GRAPH = 27,      /* 1: plk_prover_rounds_dev replays its launches as a HIP graph captured on the
-                                    first call with the same input addresses, preprocessed state and options
-                                    (per call only the scalar file and the completion word are set; a call
-                                    the graph cannot serve runs direct launches) -- measured equal, off */
   PLK_OPT_DROPIN_HOST_WORK = 28, /* drop-in headers (include/plk_host.h): a call whose host cost estimate (about
                                     ns: la*lb MACs for poly_mul, 300 per MSM point, ...) is at most this stays
                                     on the host; 32768 ~ one GPU round trip; 0: every call on the GPU.  The
@@ -117,6 +113,7 @@ enum {
                                     quotient comes from a Newton inverse over the exact poly_mul products
                                     instead of the reference's loop on one GPU thread.  0: never, 1: whenever
                                     eligible; default 256, the measured crossover */
+  /* retired (no enumerator; set: PLK_ERR_ARG, get: -1): 27 PROVE_GRAPH */
   PLK_OPT_COUNT = 30
 };
 int plk_set_option(int opt, int64_t value);   /* PLK_ERR_ARG: unknown option or value out of range */

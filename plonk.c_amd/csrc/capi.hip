@@ -453,6 +453,8 @@ struct OptDef {
   int64_t def, lo, hi;
   bool init_only;
 };
+// a retired number: never set (empty range), reads as -1 like an unknown option
+constexpr OptDef kRetired = {-1, 0, -1, false};
 const OptDef kOpt[PLK_OPT_COUNT] = {
     {0, 0, 0, false},                          // (0: unused)
     {1, 0, 1, false},                          // TINY_CALLS
@@ -481,7 +483,7 @@ const OptDef kOpt[PLK_OPT_COUNT] = {
     {1, 0, 2, false},                          // PROVE_EARLY_COMMITS (2: in round 4's evaluation launch)
     {0, 0, 1, false},                          // PROVE_HELPER_COPY (tests: the distinct-device input path on one GPU)
     {1, 0, 1, false},                          // PROVE_EVAL_AGG
-    {0, 0, 1, false},                          // PROVE_GRAPH
+    kRetired,                                  // 27
     {32768, 0, 1ll << 40, false},              // DROPIN_HOST_WORK (read by include/plk_host.h only)
     {256, 0, 1ll << 62, false},                // DIVIDE_FAST_MIN (measured crossover)
 };
@@ -564,6 +566,10 @@ int plk_set_option(int opt, int64_t value) {
     return PLK_ERR_ARG;
   }
   const OptDef& d = kOpt[opt];
+  if (d.hi < d.lo) {
+    plk_set_error("plk_set_option: option %d is retired", opt);
+    return PLK_ERR_ARG;
+  }
   if (value < d.lo || value > d.hi) {
     plk_set_error("plk_set_option(%d): %lld outside [%lld, %lld]", opt, (long long)value, (long long)d.lo,
                   (long long)d.hi);

@@ -1716,20 +1716,6 @@ struct plk_prover {
   // as a helper on another device: its copies of the 7 input polynomials it reads
   uint8_t* hin = nullptr;
   hipEvent_t ev_done = nullptr;          // (helper's device) its products have reached the proving device
-  // plk_prover_rounds_dev as a captured HIP graph (PLK_OPT_PROVE_GRAPH, rounds_graph): replayed
-  // while the inputs' addresses, the preprocessed transforms (fix_gen) and every option are the
-  // ones it was captured with; per call the first kernel's scalar file and the last kernel's
-  // completion word are set as node parameters
-  hipGraph_t g = nullptr;
-  hipGraphExec_t gx = nullptr;
-  hipGraphNode_t g_first = nullptr, g_last = nullptr;
-  int g_first_arg = -1, g_first_n = 0;
-  const uint8_t* g_pl[13] = {};
-  bool g_pre = false;
-  uint32_t fix_gen = 0, g_fix_gen = 0;
-  int64_t g_opt[PLK_OPT_COUNT] = {};
-  uint32_t g_seq = 0;              // the completion word the graph's last kernel writes
-  SlotFile g_sf{};                 // the scalar file its first kernel holds
   // plk_prover_profile_dev: events around the launch sequence [0] .. [5] and round 3's two product
   // batches ([1]-[2], [3]-[4]: every NTT pass kernel of the proof), recorded only while tev_on
   hipEvent_t tev[6] = {};
@@ -2253,7 +2239,6 @@ int create_on(const plk_plonk_desc_t* d, int dev, plk_prover_t** out) {
 
 void detach_helpers(plk_prover* P);
 
-void drop_graph(plk_prover* P);   // (rounds_graph)
 }  // namespace
 
 extern "C" {
@@ -2266,7 +2251,6 @@ void plk_prover_destroy(plk_prover_t* P) {
   DevGuard dg;
   (void)hipSetDevice(P->dev);
   if (P->st) (void)hipStreamSynchronize(P->st);
-  drop_graph(P);
   (void)hipFree(P->mem);
   (void)hipFree(P->bt_mem);
   if (P->h_res) (void)hipHostFree(P->h_res);
@@ -2826,122 +2810,6 @@ int rounds_split(plk_prover* P, const uint8_t* const* pl, const uint8_t* const* 
   return rounds(P, pl, chal, rnd, pre, md);
 }
 
-// ---- rounds() as a HIP graph (PLK_OPT_PROVE_GRAPH).  A proof is 12-14 dependent launches whose
-// host cost (~3-7 us each under a runtime trace) exceeds the GPU time of the first kernels: the GPU
-// idles after the first one until the host has enqueued the next.  rounds() enqueues the same
-// launches with the same arguments for the same input addresses, options and preprocessed state
-// -- except the scalar file (the first kernel's argument: prep_kernel or scalars_init_kernel) and
-// the completion word (the last: commit_pack_kernel or trim_pack_kernel) -- so it is captured once
-// and replayed: the scalar file set as a node parameter when it changed, the completion word
-// cleared by the host before the launch (the call is synchronous: the previous replay is done)
-// and polled for the captured value.
-void drop_graph(plk_prover* P) {
-  if (P->gx) (void)hipGraphExecDestroy(P->gx);
-  if (P->g) (void)hipGraphDestroy(P->g);
-  P->gx = nullptr;
-  P->g = nullptr;
-  P->g_first = P->g_last = nullptr;
-}
-
-bool graph_matches(const plk_prover* P, const uint8_t* const* pl, bool pre) {
-  if (!P->gx || P->g_pre != pre || P->g_fix_gen != P->fix_gen) return false;
-  for (int i = 0; i < 13; i++)
-    if (P->g_pl[i] != pl[i]) return false;
-  for (int o = 1; o < PLK_OPT_COUNT; o++)
-    if (P->g_opt[o] != plk_opt(o)) return false;
-  return true;
-}
-
-// argument idx (of nargs) of kernel node `node` set to *val in the executable graph
-int graph_set_arg(plk_prover* P, hipGraphNode_t node, int nargs, int idx, void* val) {
-  hipKernelNodeParams kp{};
-  PLK_HIP(hipGraphKernelNodeGetParams(node, &kp));
-  if (!kp.kernelParams || nargs > 16) {
-    plk_set_error("prover graph: kernel node without argument pointers");
-    return PLK_ERR_HIP;
-  }
-  void* args[16];
-  for (int i = 0; i < nargs; i++) args[i] = kp.kernelParams[i];
-  args[idx] = val;
-  kp.kernelParams = args;
-  PLK_HIP(hipGraphExecKernelNodeSetParams(P->gx, node, &kp));
-  return PLK_OK;
-}
-
-// rounds() through the graph: capture (and launch) on a key change, else set the two per-call
-// parameters and replay.  The fused division's scan epochs (PLK_OPT_PROVE_FUSE_DIV) change per
-// call inside its launch: that mode runs rounds() directly.
-int rounds_graph(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const uint8_t rnd[9], bool pre) {
-  if (graph_matches(P, pl, pre)) {
-    SlotFile sf = make_slotfile(P->n, chal, rnd);
-    if (memcmp(&sf, &P->g_sf, sizeof sf)) {
-      if (graph_set_arg(P, P->g_first, P->g_first_n, P->g_first_arg, &sf)) {
-        drop_graph(P);   // (the runtime would not take the parameter: direct launches)
-        return rounds(P, pl, chal, rnd, pre);
-      }
-      P->g_sf = sf;
-    }
-    __atomic_store_n((uint32_t*)(P->h_res + 60), 0u, __ATOMIC_SEQ_CST);
-    P->seq = P->g_seq;
-    PLK_HIP(hipGraphLaunch(P->gx, P->st));
-    return PLK_OK;
-  }
-  drop_graph(P);
-  const uint32_t epoch = P->scan_epoch, seq = P->seq;
-  // capture ran nothing: anything that keeps this call from a graph runs it with direct launches
-  auto direct = [&]() {
-    (void)hipGetLastError();
-    drop_graph(P);
-    P->seq = seq;
-    P->scan_epoch = epoch;
-    return rounds(P, pl, chal, rnd, pre);
-  };
-  if (hipStreamBeginCapture(P->st, hipStreamCaptureModeThreadLocal) != hipSuccess) return direct();
-  int rc = rounds(P, pl, chal, rnd, pre);
-  hipGraph_t g = nullptr;
-  const hipError_t e = hipStreamEndCapture(P->st, &g);
-  if (rc) {   // (an argument / range error: the same one a direct call reports)
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    P->seq = seq;
-    P->scan_epoch = epoch;
-    return rc;
-  }
-  if (e != hipSuccess || !g) {
-    if (g) (void)hipGraphDestroy(g);
-    return direct();
-  }
-  P->g = g;
-  // per-call state inside the launches (the fused division's scan epochs): no replay
-  if (P->scan_epoch != epoch || P->seq != seq + 1) return direct();
-  // the first and last kernel nodes, by function
-  size_t nn = 0;
-  if (hipGraphGetNodes(g, nullptr, &nn) != hipSuccess) return direct();
-  std::vector<hipGraphNode_t> nodes(nn);
-  if (hipGraphGetNodes(g, nodes.data(), &nn) != hipSuccess) return direct();
-  for (hipGraphNode_t nd : nodes) {
-    hipGraphNodeType t;
-    if (hipGraphNodeGetType(nd, &t) != hipSuccess || t != hipGraphNodeTypeKernel) continue;
-    hipKernelNodeParams kp{};
-    if (hipGraphKernelNodeGetParams(nd, &kp) != hipSuccess) continue;
-    if (kp.func == (void*)prep_kernel) { P->g_first = nd; P->g_first_arg = 1; P->g_first_n = 5; }
-    if (kp.func == (void*)scalars_init_kernel) { P->g_first = nd; P->g_first_arg = 0; P->g_first_n = 5; }
-    if (kp.func == (void*)commit_pack_kernel || kp.func == (void*)trim_pack_kernel) P->g_last = nd;
-  }
-  if (!P->g_first || !P->g_last || hipGraphInstantiateWithFlags(&P->gx, g, 0) != hipSuccess) {
-    P->gx = nullptr;
-    return direct();
-  }
-  for (int i = 0; i < 13; i++) P->g_pl[i] = pl[i];
-  P->g_pre = pre;
-  P->g_fix_gen = P->fix_gen;
-  for (int o = 1; o < PLK_OPT_COUNT; o++) P->g_opt[o] = plk_opt(o);
-  P->g_seq = P->seq;
-  P->g_sf = make_slotfile(P->n, chal, rnd);
-  PLK_HIP(hipGraphLaunch(P->gx, P->st));   // (this call's launches)
-  return PLK_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2953,9 +2821,7 @@ int plk_prover_rounds_dev(plk_prover_t* P, const uint8_t* const d_polys[13], con
     if (!d_polys[i]) { plk_set_error("plk_prover_rounds_dev: polynomial %d is NULL", i); return PLK_ERR_ARG; }
   const bool pre = (flags & PLK_PROVE_PREPROCESSED) != 0;
   PROVER_ON_DEVICE(P);
-  int rc = P->nhelp                         ? rounds_split(P, d_polys, nullptr, chal, rand9, pre)
-           : plk_opt(PLK_OPT_PROVE_GRAPH) ? rounds_graph(P, d_polys, chal, rand9, pre)
-                                          : rounds(P, d_polys, chal, rand9, pre);
+  int rc = P->nhelp ? rounds_split(P, d_polys, nullptr, chal, rand9, pre) : rounds(P, d_polys, chal, rand9, pre);
   if (rc) { (void)hipStreamSynchronize(P->st); return rc; }
   return finish(P, (flags & PLK_PROVE_STRICT) != 0, 0, proof);
 }
@@ -3203,7 +3069,6 @@ int plk_prover_preprocess(plk_prover_t* P, const uint8_t* const d_polys[13]) {
   if (!P) { plk_set_error("plk_prover_preprocess: NULL prover"); return PLK_ERR_ARG; }
   PROVER_ON_DEVICE(P);
   PLK_HIP(hipStreamSynchronize(P->st));   // (no round may still read the old transforms)
-  ++P->fix_gen;                            // (a captured proof graph reads the old ones: recapture)
   for (auto& f : P->fix) f = plk_prover::Fixed{};
   (void)hipFree(P->fix_mem);
   P->fix_mem = nullptr;

@@ -80,15 +80,15 @@ def test_host_argument_checks():
 
 def test_options_without_gpu():
     """plk_set_option / plk_get_option (the library's only switches besides PLK_DEVICE) work with
-    no device; defaults are the production settings; out-of-range values and unknown options
-    are refused; the library source reads no other environment variable."""
+    no device; defaults are the production settings; out-of-range values, unknown options and
+    the retired option number are refused; the library source reads no other environment variable."""
     import plonkhip as h
     defaults = {"TINY_CALLS": 1, "PROVE_SYNC": 0, "POLY_BLOCK_L": 0, "POLY_BLOCK_S": 0, "NTT_F29": 1,
                 "NTT_SHARE": 1, "NTT_SHARED_FIX": 1, "NTT_T13_MIN_K": 21, "NTT_CENTER_BLOCKS": 0,
                 "MSM_HALF": 1, "MSM_SHARD_MIN": 1 << 16, "NTT_CENTER_SUM": 1, "MSM_HOST_LANES": 4,
                 "PROVE_DERIVE_T2A": 2, "NTT_TABLE_SHARE": 1, "NTT_LAUNCH_LOG": 0,
                 "PROVE_FUSE_DIV": 0, "PROVE_SRS_LOGS": 1, "PROVE_PACK_FUSE": 1, "PROVE_EARLY_COMMITS": 1,
-                "PROVE_EVAL_AGG": 1, "PROVE_GRAPH": 0}
+                "PROVE_EVAL_AGG": 1}
     for k, v in defaults.items():
         assert h.get_option(k) == v, k
     with h.options(NTT_SHARED_FIX=2, POLY_BLOCK_L=4096, POLY_BLOCK_S=513):
@@ -99,6 +99,11 @@ def test_options_without_gpu():
             h.set_option(k, v)
         assert e.value.code == h.PLK_ERR_ARG
     assert h.get_option(99) == -1
+    assert 27 not in h.OPTIONS.values()    # number 27 is retired: no name, never set, reads as unknown
+    with pytest.raises(h.PlonkHipError) as e:
+        h.set_option(27, 0)
+    assert e.value.code == h.PLK_ERR_ARG
+    assert h.get_option(27) == -1
     csrc = os.path.join(PKG, "csrc")
     envs = set()
     for f in os.listdir(csrc):

@@ -403,15 +403,15 @@ def test_strict_accept_and_single_coefficient(hip, oracle, n, seed):
 @pytest.mark.parametrize("n,seed", STRICT_SIZES)
 def test_strict_accept_every_division_form(hip, oracle, n, seed):
     """The strict accept where the round-5 remainder words come from other kernels: the look-back
-    division, the two-launch division, graph replay, a preprocessed circuit, and the split proof
+    division, the two-launch division, a preprocessed circuit, and the split proof
     (chains_dev + rounds_ext_dev, both chains)"""
     c = _strict_case(oracle, n, seed)
     pr = hip.Prover(n, c["zh"], c["pts"])
     d = _dev(c["polys"])
     chal, rnd, want = c["chal"], c["rnd"], c["want"].hex()
-    for opt in ({"PROVE_FUSE_DIV": 1}, {"PROVE_EVAL_AGG": 0}, {"PROVE_GRAPH": 1}):
+    for opt in ({"PROVE_FUSE_DIV": 1}, {"PROVE_EVAL_AGG": 0}):
         with hip.options(**opt):
-            for _ in range(2):       # (graph: capture, then replay)
+            for _ in range(2):
                 assert pr.rounds_dev(d, chal, rnd, strict=True).hex() == want, opt
     pr.preprocess(d)
     assert pr.rounds_dev(d, chal, rnd, strict=True, preprocessed=True).hex() == want

@@ -275,8 +275,6 @@ def test_profile_and_launches_small_vs_rounds(hip):
     assert pr.rounds_dev(d, chal, rnd) == want
     assert pr.profile_dev(d, chal, rnd)[0] == want
     assert pr.rounds_dev(d, chal, rnd) == want
-    with hip.options(PROVE_GRAPH=1):
-        assert pr.rounds_dev(d, chal, rnd) == want and pr.rounds_dev(d, chal, rnd) == want
 
 
 @pytest.mark.parametrize("n,seed", [(256, 3), (3000, 5), (5000, 7), (1 << 16, 41)])
@@ -312,52 +310,6 @@ def test_derive_t2a_2_20_vs_golden(hip):
             pr.preprocess(dev)
             assert pr.rounds_dev(dev, chal, rnd, preprocessed=True).hex() == g["proof"], mode
             pr.preprocess(None)
-
-
-@pytest.mark.parametrize("n,seed", [(3000, 5), (1 << 16, 41)])
-def test_graph_replay_vs_direct(hip, n, seed):
-    """PLK_OPT_PROVE_GRAPH: the first call captures the proof's launches, later calls replay them
-    with the scalar file and the completion word set per call -- the same bytes as direct launches
-    for two challenge / blinding sets in turn, plain and preprocessed (a recapture: the fixed
-    transforms changed), after an input moved (recapture), and again with the graph off."""
-    polys, chal, rnd, zh, pts = _synthetic(n, seed, 2 * n + 8)
-    sets = [(list(chal), list(rnd)), (list(chal[1:]) + [chal[0]], list(rnd[::-1]))]
-    pr = hip.Prover(n, zh, pts)
-    dev = [torch.from_numpy(p).to("cuda") for p in polys]
-    want = [pr.rounds_dev(dev, c, r) for c, r in sets]
-    assert want[0] != want[1]
-    with hip.options(PROVE_GRAPH=1):
-        for _ in range(3):
-            for (c, r), w in zip(sets, want):
-                assert pr.rounds_dev(dev, c, r).hex() == w.hex()
-        pr.preprocess(dev)
-        for _ in range(2):
-            for (c, r), w in zip(sets, want):
-                assert pr.rounds_dev(dev, c, r, preprocessed=True).hex() == w.hex()
-        moved = list(dev)
-        moved[5] = dev[5].clone()
-        for (c, r), w in zip(sets, want):
-            assert pr.rounds_dev(moved, c, r, preprocessed=True).hex() == w.hex()
-        pr.preprocess(None)
-        assert pr.rounds_dev(dev, *sets[1]).hex() == want[1].hex()
-    # the fused look-back division changes its scan epoch per call: such calls run direct launches
-    with hip.options(PROVE_GRAPH=1, PROVE_FUSE_DIV=1):
-        for _ in range(2):
-            for (c, r), w in zip(sets, want):
-                assert pr.rounds_dev(dev, c, r).hex() == w.hex()
-    assert pr.rounds_dev(dev, *sets[0]).hex() == want[0].hex()
-
-
-def test_graph_replay_2_20_vs_golden(hip):
-    """Config C5 through the captured graph: capture, then replays, all the golden bytes."""
-    g = load_golden("prove_2_20.json")
-    n = g["n"]
-    polys, chal, rnd, zh, pts = _synthetic(n, g["seed"], g["srs_len"])
-    pr = hip.Prover(n, zh, pts)
-    dev = [torch.from_numpy(p).to("cuda") for p in polys]
-    with hip.options(PROVE_GRAPH=1):
-        for _ in range(3):
-            assert pr.rounds_dev(dev, chal, rnd).hex() == g["proof"]
 
 
 _TILE13_SCRIPT = r"""
@@ -467,7 +419,7 @@ def test_preprocessed_tensors_held_and_overwrite_needs_preprocess(hip):
 _SWEEP = [("NTT_F29", 0), ("NTT_SHARE", 0), ("NTT_SHARED_FIX", 0), ("NTT_SHARED_FIX", 2), ("NTT_CENTER_BLOCKS", 768),
           ("NTT_CENTER_SUM", 0), ("NTT_TABLE_SHARE", 0), ("PROVE_DERIVE_T2A", 0), ("PROVE_DERIVE_T2A", 1),
           ("PROVE_FUSE_DIV", 1), ("PROVE_SRS_LOGS", 0), ("PROVE_PACK_FUSE", 0), ("PROVE_EARLY_COMMITS", 0),
-          ("PROVE_EARLY_COMMITS", 2), ("PROVE_EVAL_AGG", 0), ("PROVE_GRAPH", 1), ("PROVE_SYNC", 1)]
+          ("PROVE_EARLY_COMMITS", 2), ("PROVE_EVAL_AGG", 0), ("PROVE_SYNC", 1)]
 
 
 def test_option_sweep_2_20_vs_golden(hip):
@@ -475,7 +427,7 @@ def test_option_sweep_2_20_vs_golden(hip):
     instead of F29, no shared operands, the shared-operand pass off / forced, another centre grid,
     no centre sum groups, per-array column reads, A2 B2 as a product or its own kernel, the fused
     look-back division, G1-form commitments, unfused packing, the early commitments elsewhere, the
-    two-launch division, graph replay, stream-synchronised completion -- plain and preprocessed:
+    two-launch division, stream-synchronised completion -- plain and preprocessed:
     the golden bytes every time (round 5 found a wrong-result bug behind a non-default option)."""
     g = load_golden("prove_2_20.json")
     n = g["n"]
