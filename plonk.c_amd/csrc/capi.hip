@@ -960,7 +960,7 @@ int plk_poly_eval_batch(const uint8_t* const* polys, const size_t* lens, const u
       plk_set_error("plk_poly_eval_batch: NULL polynomial %d", i);
       return PLK_ERR_ARG;
     }
-  if (tiny_ok(A.off)) {   // toy sizes: no copies, one launch per 12 evaluations, one synchronize
+  if (tiny_ok(A.off)) {   // toy sizes: no copies, one launch per 32 evaluations, one synchronize
     if (g.stage_busy) {
       PLK_HIP(hipStreamSynchronize(g.st));
       g.stage_busy = false;

@@ -172,8 +172,9 @@ def test_divide_device_api_exact_buffers(hip, oracle, kind):
 
 def _tiny_cases(seed):
     """host-call shapes on both sides of the 16 KiB toy-size path (capi.hip tiny_ok): evaluations
-    in batches over 12 (several launches), empty and raw-byte (>= 240: the reference-loop re-run)
-    polynomials, short-operand products with raw bytes and trailing cancellation"""
+    in batches of up to 29 (one launch carries 32: tests/test_polyops_edges_gpu.py goes beyond),
+    empty and raw-byte (>= 240: the reference-loop re-run) polynomials, short-operand
+    products with raw bytes and trailing cancellation"""
     rng = np.random.default_rng(seed)
     evals = []
     for t in range(6):
