@@ -97,6 +97,16 @@ void orc_msm_fold(const uint8_t *pts, const uint8_t *sc, size_t n, uint8_t *out)
   st(out, acc);
 }
 
+/* Bulk forms for tests that need 10^5 .. 10^6 expected values (one ctypes call instead of one per
+ * value): out[i] = a_i + c_i * t_i, and `count` independent folds of n points each. */
+void orc_g1_add_mul_many(const uint8_t *a, const uint8_t *t, const uint8_t *c, size_t count, uint8_t *out) {
+  for (size_t i = 0; i < count; i++) st(out + 3 * i, pt_add(ld(a + 3 * i), pt_mul(ld(t + 3 * i), c[i])));
+}
+
+void orc_msm_fold_many(const uint8_t *pts, const uint8_t *sc, size_t n, size_t count, uint8_t *out) {
+  for (size_t b = 0; b < count; b++) orc_msm_fold(pts + 3 * n * b, sc + n * b, n, out + 3 * b);
+}
+
 /* ---------------- discrete-log view of E(F101) (checker) ---------------- */
 static int dl_ready;
 static uint8_t dl_log[P_GF][P_GF]; /* 0xFF = not a point */
@@ -140,6 +150,14 @@ int orc_dlog(const uint8_t *p) {
   if (p[2] != 0 || p[0] >= P_GF || p[1] >= P_GF) return -1;
   uint8_t l = dl_log[p[0]][p[1]];
   return l == 0xFF ? -1 : l;
+}
+
+/* logs[i] = orc_dlog(pts + 3 i), 0xFF where the encoding is not canonical */
+void orc_dlog_many(const uint8_t *pts, size_t count, uint8_t *logs) {
+  for (size_t i = 0; i < count; i++) {
+    int l = orc_dlog(pts + 3 * i);
+    logs[i] = l < 0 ? 0xFF : (uint8_t)l;
+  }
 }
 
 void orc_dlog_exp(int k, uint8_t *out) { dl_init(); st(out, dl_exp[((k % 102) + 102) % 102]); }

@@ -102,6 +102,12 @@ class Oracle(_Lib):
         L.orc_dlog.restype = C.c_int
         L.orc_dlog.argtypes = [_u8p]
         L.orc_dlog_exp.argtypes = [C.c_int, _u8p]
+        L.orc_dlog_many.restype = None
+        L.orc_dlog_many.argtypes = [_u8p, C.c_size_t, _u8p]
+        L.orc_g1_add_mul_many.restype = None
+        L.orc_g1_add_mul_many.argtypes = [_u8p, _u8p, _u8p, C.c_size_t, _u8p]
+        L.orc_msm_fold_many.restype = None
+        L.orc_msm_fold_many.argtypes = [_u8p, _u8p, C.c_size_t, C.c_size_t, _u8p]
         L.orc_dlog_generator.argtypes = [_u8p]
         L.orc_poly_mul_ntt.restype = C.c_size_t
         L.orc_poly_mul_ntt.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, _u8p]
@@ -122,6 +128,30 @@ class Oracle(_Lib):
         out = np.zeros(3, np.uint8)
         self.lib.orc_msm_fold(_ptr(pts), _ptr(sc), sc.size, _ptr(out))
         return bytes(out)
+
+    def g1_add_mul_many(self, a, t, c):
+        """out[i] = g1_add(a[i], g1_mul(t[i], c[i])) for (m, 3) point arrays and m scalar bytes, as (m, 3) uint8"""
+        a, t, c = _u8(a).reshape(-1), _u8(t).reshape(-1), _u8(c).reshape(-1)
+        assert a.size == 3 * c.size and t.size == 3 * c.size
+        out = np.zeros((c.size, 3), np.uint8)
+        self.lib.orc_g1_add_mul_many(_ptr(a), _ptr(t), _ptr(c), c.size, _ptr(out))
+        return out
+
+    def msm_many(self, pts, sc):
+        """msm of every row of pts (count, n, 3) with sc (count, n), as (count, 3) uint8"""
+        pts, sc = _u8(pts), _u8(sc)
+        count, n = sc.shape
+        assert pts.shape == (count, n, 3)
+        out = np.zeros((count, 3), np.uint8)
+        self.lib.orc_msm_fold_many(_ptr(pts), _ptr(sc), n, count, _ptr(out))
+        return out
+
+    def dlog_many(self, pts):
+        """discrete log per point of pts (m, 3), 0xFF where the encoding is not canonical"""
+        pts = _u8(pts).reshape(-1)
+        out = np.zeros(pts.size // 3, np.uint8)
+        self.lib.orc_dlog_many(_ptr(pts), out.size, _ptr(out))
+        return out
 
     def msm_dlog(self, pts, sc):
         """(log, G1 bytes) for canonical on-curve inputs; (None, None) if irregular."""
@@ -226,6 +256,21 @@ class Reference(_Lib):
         out = np.zeros(3, np.uint8)
         self.lib.ref_msm(_ptr(pts), _ptr(sc), sc.size, _ptr(out))
         return bytes(out)
+
+    def msm_many(self, pts, sc):
+        """ref_msm of every row of pts (count, n, 3) with sc (count, n), as (count, 3) uint8: one
+        call per row on raw addresses (no per-call array marshalling)"""
+        pts, sc = _u8(pts), _u8(sc)
+        count, n = sc.shape
+        assert pts.shape == (count, n, 3)
+        out = np.zeros((count, 3), np.uint8)
+        f = C.CDLL(self.path).ref_msm          # a second binding of the same library: integer addresses
+        f.restype = None
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        p0, s0, o0 = pts.ctypes.data, sc.ctypes.data, out.ctypes.data
+        for i in range(count):
+            f(p0 + 3 * n * i, s0 + n * i, n, o0 + 3 * i)
+        return out
 
     def poly_mul_ntt_blocked(self, a, b, piece):
         """orc_poly_mul_ntt_blocked: the shorter operand in pieces of at most `piece` coefficients"""
