@@ -340,6 +340,46 @@ int plk_kzg_open_batch_dev(const plk_srs_t *s, const uint8_t *const *d_polys, co
                            uint8_t *const *d_quots /* NULL, or per job NULL / max(len-1,1) bytes */,
                            void *d_work, void *stream);
 
+/* ---- Pairings and KZG verification: batched, one lane per job ----------------------------
+ * The reference's pairing() (src/pairing.h:66-83) over n independent (G1, G2) pairs in one launch,
+ * and the check of a KZG opening (C, z, y, W) built from it.  All group arithmetic of the check is
+ * in G1 (the reference's G2 has no identity encoding, which sH - zH would need at z = s):
+ *     L  = C - y G + z W                        G = [1]_1, W = the proof
+ *     ok = pairing(L, [1]_2) == pairing(W, [s]_2)
+ * Only KZG openings are verified.  No verifier of the reference's PLONK proofs is offered, because
+ * none can be sound: plonk_prove's linearisation contains a product of two committed polynomials
+ * (src/plonk.h:557-564), so a verifier cannot form [r]_1 from the commitments.
+ *
+ * Encodings: G1 3 bytes {x, y, infinite} as everywhere; G2 2 bytes {x, y} (src/g2.h:7-9); GT 2 bytes
+ * {a, b} = a + b u with u^2 = -2 (src/gt.h:7-9).  Valid: G1 x, y < 101 and flag 0 or 1 -- on the
+ * curve or off it, and an identity flag with non-zero coordinates is allowed; G2 x, y < 101;
+ * z, y < 17.
+ *
+ * Semantics (the specification; job b of a batch of n):
+ *   pairing  a valid pair gives the reference's pairing() bytes exactly.  The reference applies its
+ *            formulas blindly and so does the kernel: no curve-membership test, no subgroup test.
+ *            An invalid pair gives {0xFF, 0xFF}; its batch neighbours are unaffected.
+ *   verify   ok[b] = gtp_equal(pairing(&L, &vk->g2_1), pairing(&W, &vk->g2_s)), 1 or 0, with
+ *                yG = g1_mul(&G, y); nyG = g1_neg(&yG); zW = g1_mul(&W, z);
+ *                L = g1_add(&C, &nyG); L = g1_add(&L, &zW);         (G = vk->g1)
+ *            A job with an invalid byte in C, W, z or y gets ok[b] = 2; its neighbours are unaffected.
+ * The verification key is 7 bytes read at the call: no handle, not tied to plk_srs_t (a verifier
+ * never holds the SRS).  Host forms are synchronous and run on the library's primary device, which
+ * they make the calling thread's current device as the other host-buffer entry points do.  _dev forms
+ * are asynchronous on `stream`, need no workspace, keep no state and use no atomics; their pointers
+ * may have any alignment; the calling thread's current device must be the library's (the pointers and
+ * the stream belong to it).
+ * Errors: a NULL pointer, n == 0 or an invalid byte in vk are PLK_ERR_ARG, n > 2^30 is PLK_ERR_RANGE
+ * (both before any device query); no GPU is PLK_ERR_NODEV -- there is no CPU fallback; a _dev call
+ * from a thread whose current device is not the library's is PLK_ERR_ARG. */
+typedef struct { uint8_t g1[3]; uint8_t g2_1[2]; uint8_t g2_s[2]; uint8_t pad; } plk_kzg_vk_t;  /* 8 bytes: [1]_1, [1]_2, [s]_2 */
+int plk_pairing_batch(const uint8_t *g1s /* 3 n */, const uint8_t *g2s /* 2 n */, size_t n, uint8_t *out_gt /* 2 n */);
+int plk_pairing_batch_dev(const uint8_t *d_g1s, const uint8_t *d_g2s, size_t n, uint8_t *d_out_gt, void *stream);
+int plk_kzg_verify_batch(const plk_kzg_vk_t *vk, const uint8_t *commits3, const uint8_t *zs, const uint8_t *ys,
+                         const uint8_t *proofs3, size_t n, uint8_t *ok /* n */);
+int plk_kzg_verify_batch_dev(const plk_kzg_vk_t *vk /* HOST */, const uint8_t *d_commits3, const uint8_t *d_zs,
+                             const uint8_t *d_ys, const uint8_t *d_proofs3, size_t n, uint8_t *d_ok, void *stream);
+
 /* ---- device-resident prover (replaces plonk_new / plonk_prove / plonk_free,
  * src/plonk.h:53-139, 223-656, 120-139) ---------------------------------------------------
  * plk_prover_create uploads the SRS and Z_H once (the PLONK struct of plonk_new); the

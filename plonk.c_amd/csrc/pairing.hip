@@ -1,0 +1,304 @@
+// Batched pairings and KZG opening verification (include/plonkhip.h, "Pairings and KZG verification").
+//
+// One lane per job, nothing shared between lanes but the block's table of GF(101) inverses: no
+// workspace, no state, no atomics, no cross-lane or cross-block traffic.
+//
+//   pairing  the reference's pairing(p, q) (src/pairing.h:66-83).  pairing_f(17) unrolls to the fixed
+//            schedule r = 2, 4, 8, 16, 17; the multiples it asks g1_mul for are 2^k p, which for every
+//            valid encoding are k repeated g1_doubles, so one chain p, 2p, 4p, 8p, 16p serves the loop:
+//              f <- f^2 * line(2^k p, g1_double(g1_neg(2^k p)))(q)     k = 0 .. 3
+//              f <- f   * line(16 p, p)(q)
+//            and the final power 600 = (101^2 - 1) / 17 is gtp_pow's >= 101 branch, conj(f^5) * f^95.
+//            The formulas are applied blindly, as the reference applies them: no curve test, no subgroup
+//            test, and line() reads x and y whatever the flag says.
+//   verify   L = C - y G + z W built with the raw g1_mul / g1_neg / g1_add in the order the header
+//            fixes, then pairing(L, [1]_2) == pairing(W, [s]_2), all in registers, one byte out.
+//
+// The raw G1 formulas are restated here after RawOps of msm.hip (which stays untouched); every
+// select is branch-free so the lanes of a wave do not diverge on the encodings they hold.  The
+// inverse table (inv(0) = 0, gf_inv is v^99) is indexed per lane, so it lives in LDS; each block
+// computes it itself, one power per thread, which keeps the entry points free of any table upload.
+#include <algorithm>
+
+#include "plk_internal.h"
+
+namespace {
+
+constexpr uint32_t GFP = 101, HFP = 17;
+constexpr int PAIR_T = 256;
+constexpr uint32_t PAIR_MAX_BLOCKS = 2048;   // 8 blocks per CU; larger batches run the grid-stride loop
+constexpr size_t PAIR_MAX_N = (size_t)1 << 30;
+
+struct Pt { uint32_t x, y, inf; };
+struct Gt { uint32_t a, b; };
+struct VkWords { uint32_t gx, gy, ginf, h1x, h1y, hsx, hsy; };
+
+// v mod 101 for v < 33554: 41529 = ceil(2^22 / 101), 101 * 41529 - 2^22 = 125 and 2^22 / 125 > 33554
+__device__ __forceinline__ uint32_t red(uint32_t v) { return v - GFP * ((v * 41529u) >> 22); }
+__device__ __forceinline__ uint32_t sub(uint32_t a, uint32_t b) { const uint32_t d = a + GFP - b; return d >= GFP ? d - GFP : d; }
+__device__ __forceinline__ uint32_t neg(uint32_t a) { return a ? GFP - a : 0u; }
+
+// the block's inverse table: thread v computes v^99
+__device__ __forceinline__ void stage_inverses(uint32_t* invl) {
+  for (uint32_t v = threadIdx.x; v < GFP; v += PAIR_T) {
+    uint32_t r = 1, b = v;
+#pragma unroll
+    for (uint32_t e = GFP - 2; e; e >>= 1) {
+      if (e & 1u) r = red(r * b);
+      b = red(b * b);
+    }
+    invl[v] = r;
+  }
+  __syncthreads();
+}
+
+struct G1Ops {
+  const uint32_t* inv;   // LDS
+  // g1_double (src/g1.h:37-56); the formula runs for every lane (inv(0) = 0) and the identity is selected after
+  __device__ __forceinline__ Pt dbl(Pt a) const {
+    const uint32_t two_y = a.y + a.y;
+    const uint32_t m = red(red(3u * a.x * a.x) * inv[two_y >= GFP ? two_y - GFP : two_y]);
+    const uint32_t m2 = red(m * m);
+    const uint32_t xr = red(m2 + 2u * GFP - 2u * a.x);
+    const uint32_t yr = red(m * red(3u * a.x + GFP - m2) + GFP - a.y);
+    const bool id = a.inf || a.y == 0;
+    return Pt{id ? 0u : xr, id ? 0u : yr, id ? 1u : 0u};
+  }
+  // g1_add (src/g1.h:59-83)
+  __device__ __forceinline__ Pt add(Pt a, Pt b) const {
+    const uint32_t m = red((b.y + GFP - a.y) * inv[sub(b.x, a.x)]);
+    const uint32_t xr = red(m * m + 2u * GFP - a.x - b.x);
+    const uint32_t yr = red(m * sub(a.x, xr) + GFP - a.y);
+    const Pt d = dbl(a);
+    Pt r{xr, yr, 0};
+    if (a.x == b.x) {
+      const uint32_t s = a.y + b.y;
+      const bool opposite = s == 0 || s == GFP;
+      r = opposite ? Pt{0, 0, 1} : d;
+    }
+    if (b.inf) r = a;
+    if (a.inf) r = b;
+    return r;
+  }
+  // g1_neg (src/g1.h:85-89): a flagged point is returned as it is, coordinates included
+  __device__ __forceinline__ Pt negp(Pt a) const { return Pt{a.x, a.inf ? a.y : neg(a.y), a.inf}; }
+  // g1_mul (src/g1.h:91-103) for k < 32: a zero bit leaves the sum alone, so five fixed steps
+  __device__ __forceinline__ Pt mul(Pt run, uint32_t k) const {
+    Pt term{0, 0, 1};
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+      const Pt t = add(term, run);
+      if ((k >> i) & 1u) term = t;
+      run = dbl(run);
+    }
+    return term;
+  }
+};
+
+// gtp_mul (src/gt.h:23-28): (a + b u)(c + d u), u^2 = -2; 20402 = 2 * 101^2 keeps the difference positive
+__device__ __forceinline__ Gt gt_mul(Gt f, Gt g) {
+  return Gt{red(f.a * g.a + 20402u - 2u * f.b * g.b), red(f.a * g.b + f.b * g.a)};
+}
+
+// line(a, b) (src/pairing.h:19-29) evaluated at q as pairing_f does (src/pairing.h:41-44)
+__device__ __forceinline__ Gt line_at(Pt a, Pt b, uint32_t qx, uint32_t qy) {
+  const uint32_t m = sub(b.x, a.x), n = sub(b.y, a.y);
+  const uint32_t c = red(m * a.y + GFP * GFP - n * a.x);
+  return Gt{red(qx * n + c), red(qy * neg(m))};
+}
+
+__device__ __forceinline__ Gt pairing(const G1Ops& G, Pt p, uint32_t qx, uint32_t qy) {
+  Gt f{1, 0};
+  Pt d = p;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {   // r = 2, 4, 8, 16
+    f = gt_mul(gt_mul(f, f), line_at(d, G.dbl(G.negp(d)), qx, qy));
+    d = G.dbl(d);
+  }
+  f = gt_mul(f, line_at(d, p, qx, qy));   // r = 17
+  // f^600 = conj(f^5) f^95, 95 = 64 + 16 + 8 + 4 + 2 + 1
+  const Gt f2 = gt_mul(f, f), f4 = gt_mul(f2, f2), f8 = gt_mul(f4, f4), f16 = gt_mul(f8, f8), f32 = gt_mul(f16, f16),
+           f64 = gt_mul(f32, f32);
+  const Gt f5 = gt_mul(f, f4);
+  const Gt f95 = gt_mul(gt_mul(gt_mul(f5, f2), gt_mul(f8, f16)), f64);
+  return gt_mul(Gt{f5.a, neg(f5.b)}, f95);
+}
+
+// a G1 from its three bytes (any alignment: byte loads, nothing read past the array); ok: valid encoding,
+// and an invalid one is replaced by the identity so that no formula sees a value >= 101
+__device__ __forceinline__ Pt load_g1(const uint8_t* p, bool& ok) {
+  const uint32_t x = p[0], y = p[1], f = p[2];
+  const bool v = x < GFP && y < GFP && f < 2u;
+  ok = ok && v;
+  return v ? Pt{x, y, f} : Pt{0, 0, 1};
+}
+
+__global__ __launch_bounds__(PAIR_T) void pairing_kernel(const uint8_t* __restrict__ g1s, const uint8_t* __restrict__ g2s,
+                                                        size_t n, uint8_t* __restrict__ out) {
+  __shared__ uint32_t invl[GFP];
+  stage_inverses(invl);
+  const G1Ops G{invl};
+  for (size_t i = (size_t)blockIdx.x * PAIR_T + threadIdx.x; i < n; i += (size_t)gridDim.x * PAIR_T) {
+    bool ok = true;
+    const Pt p = load_g1(g1s + 3 * i, ok);
+    uint32_t qx = g2s[2 * i], qy = g2s[2 * i + 1];
+    if (qx >= GFP || qy >= GFP) {
+      ok = false;
+      qx = qy = 0;
+    }
+    const Gt e = pairing(G, p, qx, qy);
+    out[2 * i] = (uint8_t)(ok ? e.a : 0xFFu);
+    out[2 * i + 1] = (uint8_t)(ok ? e.b : 0xFFu);
+  }
+}
+
+__global__ __launch_bounds__(PAIR_T) void kzg_verify_kernel(VkWords vk, const uint8_t* __restrict__ commits,
+                                                           const uint8_t* __restrict__ zs, const uint8_t* __restrict__ ys,
+                                                           const uint8_t* __restrict__ proofs, size_t n,
+                                                           uint8_t* __restrict__ okb) {
+  __shared__ uint32_t invl[GFP];
+  stage_inverses(invl);
+  const G1Ops G{invl};
+  const Pt g{vk.gx, vk.gy, vk.ginf};
+  for (size_t i = (size_t)blockIdx.x * PAIR_T + threadIdx.x; i < n; i += (size_t)gridDim.x * PAIR_T) {
+    bool ok = true;
+    const Pt c = load_g1(commits + 3 * i, ok);
+    const Pt w = load_g1(proofs + 3 * i, ok);
+    uint32_t z = zs[i], y = ys[i];
+    if (z >= HFP || y >= HFP) {
+      ok = false;
+      z = y = 0;
+    }
+    Pt l = G.add(c, G.negp(G.mul(g, y)));
+    l = G.add(l, G.mul(w, z));
+    const Gt lhs = pairing(G, l, vk.h1x, vk.h1y);
+    const Gt rhs = pairing(G, w, vk.hsx, vk.hsy);
+    okb[i] = (uint8_t)(!ok ? 2u : (lhs.a == rhs.a && lhs.b == rhs.b) ? 1u : 0u);
+  }
+}
+
+uint32_t blocks_for(size_t n) { return (uint32_t)std::min<size_t>((n + PAIR_T - 1) / PAIR_T, PAIR_MAX_BLOCKS); }
+
+// the checks that come before any device query
+int check_n(const char* fn, bool null_arg, size_t n) {
+  if (null_arg || n == 0) {
+    plk_set_error("%s: every pointer and n > 0 are required", fn);
+    return PLK_ERR_ARG;
+  }
+  return PLK_OK;
+}
+int check_range(const char* fn, size_t n) {
+  if (n > PAIR_MAX_N) {
+    plk_set_error("%s: n = %zu exceeds 2^30 jobs per call", fn, n);
+    return PLK_ERR_RANGE;
+  }
+  return PLK_OK;
+}
+int check_vk(const char* fn, const plk_kzg_vk_t* vk, VkWords* w) {
+  if (vk->g1[0] >= GFP || vk->g1[1] >= GFP || vk->g1[2] > 1 || vk->g2_1[0] >= GFP || vk->g2_1[1] >= GFP ||
+      vk->g2_s[0] >= GFP || vk->g2_s[1] >= GFP) {
+    plk_set_error("%s: the verification key holds an invalid encoding (coordinates < 101, flag 0 or 1)", fn);
+    return PLK_ERR_ARG;
+  }
+  *w = VkWords{vk->g1[0], vk->g1[1], vk->g1[2], vk->g2_1[0], vk->g2_1[1], vk->g2_s[0], vk->g2_s[1]};
+  return PLK_OK;
+}
+
+// _dev forms: the library initialised (PLK_ERR_NODEV without a GPU) and the calling thread on its
+// device (PLK_ERR_ARG otherwise: the caller's pointers and stream belong to a device).  The retain is
+// only that check -- the kernels read no library table, so nothing needs holding and it is released
+// at once.
+int use_device(void) {
+  const int rc = plk_ctx_retain();
+  if (rc) return rc;
+  plk_ctx_release();
+  return PLK_OK;
+}
+
+// host forms: initialise if need be and make the library's primary device the calling thread's
+// current one, as the other host-buffer entry points do
+int select_device(void) {
+  int rc = plk_init(-1), dev = 0;
+  if (rc) return rc;
+  if (plk_devices(&dev, 1) < 1) {
+    plk_set_error("libplonkhip was shut down during the call");
+    return PLK_ERR_HIP;
+  }
+  PLK_HIP(hipSetDevice(dev));
+  return PLK_OK;
+}
+
+// device scratch of one host-buffer call, released on scope exit
+struct Scratch {
+  uint8_t* d = nullptr;
+  ~Scratch() {
+    if (d) (void)hipFree(d);
+  }
+  int alloc(const char* fn, size_t bytes) {
+    if (hipMalloc((void**)&d, bytes) != hipSuccess) {
+      d = nullptr;
+      plk_set_error("%s: hipMalloc(%zu) failed", fn, bytes);
+      return PLK_ERR_NOMEM;
+    }
+    return PLK_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int plk_pairing_batch_dev(const uint8_t* d_g1s, const uint8_t* d_g2s, size_t n, uint8_t* d_out_gt, void* stream) {
+  const char* fn = "plk_pairing_batch_dev";
+  int rc = check_n(fn, !d_g1s || !d_g2s || !d_out_gt, n);
+  if (rc || (rc = check_range(fn, n)) || (rc = use_device())) return rc;
+  hipLaunchKernelGGL(pairing_kernel, dim3(blocks_for(n)), dim3(PAIR_T), 0, (hipStream_t)stream, d_g1s, d_g2s, n, d_out_gt);
+  PLK_HIP(hipGetLastError());
+  return PLK_OK;
+}
+
+int plk_kzg_verify_batch_dev(const plk_kzg_vk_t* vk, const uint8_t* d_commits3, const uint8_t* d_zs, const uint8_t* d_ys,
+                             const uint8_t* d_proofs3, size_t n, uint8_t* d_ok, void* stream) {
+  const char* fn = "plk_kzg_verify_batch_dev";
+  VkWords w;
+  int rc = check_n(fn, !vk || !d_commits3 || !d_zs || !d_ys || !d_proofs3 || !d_ok, n);
+  if (rc || (rc = check_vk(fn, vk, &w)) || (rc = check_range(fn, n)) || (rc = use_device())) return rc;
+  hipLaunchKernelGGL(kzg_verify_kernel, dim3(blocks_for(n)), dim3(PAIR_T), 0, (hipStream_t)stream, w, d_commits3, d_zs, d_ys,
+                     d_proofs3, n, d_ok);
+  PLK_HIP(hipGetLastError());
+  return PLK_OK;
+}
+
+int plk_pairing_batch(const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t* out_gt) {
+  const char* fn = "plk_pairing_batch";
+  int rc = check_n(fn, !g1s || !g2s || !out_gt, n);
+  if (rc || (rc = check_range(fn, n)) || (rc = select_device())) return rc;
+  Scratch S;
+  if ((rc = S.alloc(fn, 7 * n))) return rc;
+  uint8_t *d_g1 = S.d, *d_g2 = S.d + 3 * n, *d_out = S.d + 5 * n;
+  PLK_HIP(hipMemcpy(d_g1, g1s, 3 * n, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_g2, g2s, 2 * n, hipMemcpyHostToDevice));
+  if ((rc = plk_pairing_batch_dev(d_g1, d_g2, n, d_out, nullptr))) return rc;
+  PLK_HIP(hipMemcpy(out_gt, d_out, 2 * n, hipMemcpyDeviceToHost));
+  return PLK_OK;
+}
+
+int plk_kzg_verify_batch(const plk_kzg_vk_t* vk, const uint8_t* commits3, const uint8_t* zs, const uint8_t* ys,
+                         const uint8_t* proofs3, size_t n, uint8_t* ok) {
+  const char* fn = "plk_kzg_verify_batch";
+  VkWords w;
+  int rc = check_n(fn, !vk || !commits3 || !zs || !ys || !proofs3 || !ok, n);
+  if (rc || (rc = check_vk(fn, vk, &w)) || (rc = check_range(fn, n)) || (rc = select_device())) return rc;
+  Scratch S;
+  if ((rc = S.alloc(fn, 9 * n))) return rc;
+  uint8_t *d_c = S.d, *d_w = S.d + 3 * n, *d_z = S.d + 6 * n, *d_y = S.d + 7 * n, *d_ok = S.d + 8 * n;
+  PLK_HIP(hipMemcpy(d_c, commits3, 3 * n, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_w, proofs3, 3 * n, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_z, zs, n, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_y, ys, n, hipMemcpyHostToDevice));
+  if ((rc = plk_kzg_verify_batch_dev(vk, d_c, d_z, d_y, d_w, n, d_ok, nullptr))) return rc;
+  PLK_HIP(hipMemcpy(ok, d_ok, n, hipMemcpyDeviceToHost));
+  return PLK_OK;
+}
+
+}  // extern "C"

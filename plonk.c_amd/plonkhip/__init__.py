@@ -103,6 +103,10 @@ SIGNATURES = {
     "plk_kzg_commit_batch_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), C.c_int, _vp, _vp]),
     "plk_kzg_open_batch_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _u8p, C.c_int, _vp, _vp,
                                          C.POINTER(_vp), _vp, _vp]),
+    "plk_pairing_batch": (C.c_int, [_u8p, _u8p, _sz, _u8p]),
+    "plk_pairing_batch_dev": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
+    "plk_kzg_verify_batch": (C.c_int, [_vp, _u8p, _u8p, _u8p, _u8p, _sz, _u8p]),
+    "plk_kzg_verify_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
 }
 
 # PLK_OPT_* (include/plonkhip.h), by the name without the prefix
@@ -599,6 +603,50 @@ def kzg_open_dev(srs, polys, lens, zs, ys, res, quots=None, work=None, stream=No
     qs = None if quots is None else (_vp * max(n, 1))(*[_ptr(q) for q in quots])
     _check("plk_kzg_open_batch_dev", lib().plk_kzg_open_batch_dev(_srs_h(srs), ptrs, ls, _p(za), n, _ptr(ys),
                                                                   _ptr(res), qs, _ptr(work), _stream(stream)))
+
+
+# ---------------------------------------------------------------- pairings and KZG verification
+class KzgVk(C.Structure):
+    """plk_kzg_vk_t: [1]_1 (3 bytes), [1]_2 and [s]_2 (2 bytes each); KzgVk((1, 2, 0), (36, 31), (90, 82))"""
+    _fields_ = [("g1", C.c_uint8 * 3), ("g2_1", C.c_uint8 * 2), ("g2_s", C.c_uint8 * 2), ("pad", C.c_uint8)]
+
+    def __init__(self, g1, g2_1, g2_s):
+        super().__init__((C.c_uint8 * 3)(*bytes(g1)), (C.c_uint8 * 2)(*bytes(g2_1)), (C.c_uint8 * 2)(*bytes(g2_s)), 0)
+
+
+def pairing(g1s, g2s):
+    """plk_pairing_batch: n x 2 GT bytes {a, b} of pairing(g1s[i], g2s[i]); FF FF for an invalid encoding"""
+    p, q = _u8(g1s).reshape(-1), _u8(g2s).reshape(-1)
+    if p.size % 3 or q.size % 2 or p.size // 3 != q.size // 2:
+        raise ValueError("n x 3 bytes of G1 and n x 2 bytes of G2")
+    n = p.size // 3
+    out = np.zeros(2 * max(n, 1), np.uint8)
+    _check("plk_pairing_batch", lib().plk_pairing_batch(_p(p), _p(q), n, _p(out)))
+    return out[:2 * n].reshape(n, 2)
+
+
+def pairing_dev(g1s, g2s, n, out, stream=None):
+    """g1s (3 n), g2s (2 n), out (2 n): device tensors (or raw pointers) of any alignment"""
+    _check("plk_pairing_batch_dev", lib().plk_pairing_batch_dev(_ptr(g1s), _ptr(g2s), int(n), _ptr(out),
+                                                                _stream(stream)))
+
+
+def kzg_verify(vk, commits, zs, ys, proofs):
+    """plk_kzg_verify_batch: n bytes, 1 accept / 0 reject / 2 an invalid byte in the job"""
+    c, w = _u8(commits).reshape(-1), _u8(proofs).reshape(-1)
+    za, ya = _u8(zs).reshape(-1), _u8(ys).reshape(-1)
+    n = za.size
+    if c.size != 3 * n or w.size != 3 * n or ya.size != n:
+        raise ValueError("n commitments and proofs of 3 bytes, n bytes of z and of y")
+    ok = np.zeros(max(n, 1), np.uint8)
+    _check("plk_kzg_verify_batch", lib().plk_kzg_verify_batch(C.byref(vk), _p(c), _p(za), _p(ya), _p(w), n, _p(ok)))
+    return ok[:n]
+
+
+def kzg_verify_dev(vk, commits, zs, ys, proofs, n, ok, stream=None):
+    """vk: a KzgVk on the host; the rest device tensors (or raw pointers) of any alignment; ok: n bytes"""
+    _check("plk_kzg_verify_batch_dev", lib().plk_kzg_verify_batch_dev(
+        C.byref(vk), _ptr(commits), _ptr(zs), _ptr(ys), _ptr(proofs), int(n), _ptr(ok), _stream(stream)))
 
 
 # ---------------------------------------------------------------- device prover
