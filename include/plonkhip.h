@@ -380,6 +380,72 @@ int plk_kzg_verify_batch(const plk_kzg_vk_t *vk, const uint8_t *commits3, const 
 int plk_kzg_verify_batch_dev(const plk_kzg_vk_t *vk /* HOST */, const uint8_t *d_commits3, const uint8_t *d_zs,
                              const uint8_t *d_ys, const uint8_t *d_proofs3, size_t n, uint8_t *d_ok, void *stream);
 
+/* ---- KZG folded openings: k polynomials at one point, one proof ---------------------------
+ * The form KZG-based protocols use (the reference's plonk_prove round 5, src/plonk.h:582-621):
+ * polynomials p_0 .. p_{k-1} opened at the same z under caller-chosen weights w_i with ONE proof, the
+ * commitment of (sum_i w_i (p_i - p_i(z))) / (x - z), and that proof verified against the k
+ * commitments with two pairings.
+ *
+ * Opening.  The polynomials of a call lie in flat arrays; group g = entries [start[g], start[g+1]),
+ * start[0] = 0, strictly increasing, 1 .. PLK_KZG_FOLD_MAX entries a group, ngroups >= 1,
+ * npolys = start[ngroups].  For group g with L = the largest of its lens and z = zs[g] (the
+ * specification):
+ *   ys[i]      = plk_poly_eval(p_i, lens[i], z)                    for every polynomial of the group
+ *   F[j]       = the hf_add fold over i of hf_mul(w_i, p_i[j]), j < L, a polynomial contributing
+ *                nothing past its own length (the reference's poly_scale / poly_add without the trim;
+ *                hf_mul reduces, so F depends on the bytes mod 17 only and is always canonical)
+ *   proofs3[g] = the proof plk_kzg_open_batch gives for (F, L, z) -- which covers all weights zero,
+ *                F cancelling to a shorter degree or to zero, L = 1, and an irregular SRS
+ *   d_quots[g] = max(L - 1, 1) untrimmed bytes of (F - F(z)) / (x - z), exact for EVERY coefficient
+ *                byte and any SRS (F is canonical whatever the input bytes)
+ * The fast path is one fused pass: F is formed in registers (sum_i w_i x byte is exact in 16 bits,
+ * one reduction per coefficient) and handed to the opening kernel's suffix scan; an aggregates launch
+ * in front of it when some L > 4096.  A launch carries whole groups, up to 32 polynomials; larger
+ * batches run in consecutive launches on the stream.
+ *   Host form (synchronous): a group holding a coefficient byte >= 17, and every group when
+ *   plk_srs_irregular, returns the composition's bytes: its ys through plk_poly_eval, its proof the
+ *   commitment of the (exact) quotient bytes over the resident G1 form, as plk_kzg_open_batch does.
+ *   _dev form (asynchronous; d_polys / d_quots HOST arrays of device pointers; lens, weights, start
+ *   and zs HOST arrays): a group holding a coefficient byte >= 17 is left with d_res[g].irregular > 0
+ *   and g1 invalid (the convention of plk_msm_g1_dev); its d_ys are unspecified, its d_quots still
+ *   exact.  With an irregular SRS every record is flagged while ys and quotients stay exact.  Other
+ *   groups are unaffected.  Records: zeroed once, then reusable.  d_work:
+ *   plk_kzg_fold_workspace(lens, start, ngroups) bytes, no initialisation needed; may be NULL when
+ *   every L <= 4096.
+ * Errors (all but the last checked before any device query): a NULL handle or array, ngroups <= 0, a
+ * start that does not rise strictly from 0, a group of more than PLK_KZG_FOLD_MAX, lens[i] == 0, a
+ * weight or z >= 17 or a call from another device are PLK_ERR_ARG; max(L - 1, 1) > plk_srs_len or a
+ * length beyond what one record's finish can count is PLK_ERR_RANGE; no GPU is PLK_ERR_NODEV.
+ *
+ * Verification.  k is uniform over a call (its batches are many tiny jobs, one lane each): job b owns
+ * entries [k b, k (b + 1)) of commits3 / weights / ys.  With the reference's raw formulas applied
+ * blindly, as plk_kzg_verify_batch applies them (the specification):
+ *   acc = g1_identity();  for i in order: term = g1_mul(&C_i, w_i); acc = g1_add(&acc, &term);
+ *   y   = the hf_add fold of hf_mul(w_i, y_i) from hf_zero()
+ *   ok[b] = the check of plk_kzg_verify_batch on (C = acc, z, y, W)
+ * A job with an invalid byte (a G1 coordinate >= 101, a G1 flag > 1, a weight, y or z >= 17) gets
+ * ok[b] = 2; its neighbours are unaffected.  k = 1 with w = 1 goes through
+ * g1_add(identity, g1_mul(C, 1)), which need not return an off-curve or flagged C byte for byte.
+ * Errors: k < 1, k > PLK_KZG_FOLD_MAX, a NULL pointer, n == 0 or an invalid byte in vk are
+ * PLK_ERR_ARG, n k > 2^30 is PLK_ERR_RANGE (both before any device query); no GPU is PLK_ERR_NODEV;
+ * the device rules are those of plk_kzg_verify_batch(_dev). */
+#define PLK_KZG_FOLD_MAX 16   /* polynomials per group */
+size_t plk_kzg_fold_workspace(const size_t *lens, const int *start, int ngroups);   /* host only; 0 for bad arguments */
+int plk_kzg_open_fold_batch(const plk_srs_t *s, const uint8_t *const *polys, const size_t *lens,
+                            const uint8_t *weights /* npolys */, const int *start, const uint8_t *zs /* ngroups */,
+                            int ngroups, uint8_t *ys /* npolys */, uint8_t *proofs3 /* 3 ngroups */);
+int plk_kzg_open_fold_batch_dev(const plk_srs_t *s, const uint8_t *const *d_polys, const size_t *lens,
+                                const uint8_t *weights, const int *start, const uint8_t *zs, int ngroups,
+                                uint8_t *d_ys, plk_msm_result_t *d_res /* ngroups */,
+                                uint8_t *const *d_quots /* NULL, or per group NULL / max(L-1,1) bytes */,
+                                void *d_work, void *stream);
+int plk_kzg_verify_fold_batch(const plk_kzg_vk_t *vk, int k, const uint8_t *commits3, const uint8_t *weights,
+                              const uint8_t *ys, const uint8_t *zs /* n */, const uint8_t *proofs3 /* 3 n */,
+                              size_t n, uint8_t *ok /* n */);
+int plk_kzg_verify_fold_batch_dev(const plk_kzg_vk_t *vk /* HOST */, int k, const uint8_t *d_commits3,
+                                  const uint8_t *d_weights, const uint8_t *d_ys, const uint8_t *d_zs,
+                                  const uint8_t *d_proofs3, size_t n, uint8_t *d_ok, void *stream);
+
 /* ---- device-resident prover (replaces plonk_new / plonk_prove / plonk_free,
  * src/plonk.h:53-139, 223-656, 120-139) ---------------------------------------------------
  * plk_prover_create uploads the SRS and Z_H once (the PLONK struct of plonk_new); the

@@ -13,6 +13,8 @@
 //            test, and line() reads x and y whatever the flag says.
 //   verify   L = C - y G + z W built with the raw g1_mul / g1_neg / g1_add in the order the header
 //            fixes, then pairing(L, [1]_2) == pairing(W, [s]_2), all in registers, one byte out.
+//   fold     the same check on C = the raw fold of g1_mul(C_i, w_i) over a job's k commitments and
+//            y = sum_i w_i y_i: k uniform over the launch, so every lane runs the same k steps.
 //
 // The raw G1 formulas are restated here after RawOps of msm.hip (which stays untouched); every
 // select is branch-free so the lanes of a wave do not diverge on the encodings they hold.  The
@@ -177,6 +179,48 @@ __global__ __launch_bounds__(PAIR_T) void kzg_verify_kernel(VkWords vk, const ui
   }
 }
 
+// Folded verification, job i: C = the fold of its k commitments under its k weights and y = the fold
+// of its k values, built with the raw g1_mul / g1_add from the identity in entry order (as
+// srs_eval_at_s folds), then the check of kzg_verify_kernel.  k is uniform over the launch, so the
+// loop's trip count is the same in every lane.
+__global__ __launch_bounds__(PAIR_T) void kzg_verify_fold_kernel(VkWords vk, uint32_t k, const uint8_t* __restrict__ commits,
+                                                                const uint8_t* __restrict__ weights,
+                                                                const uint8_t* __restrict__ ys, const uint8_t* __restrict__ zs,
+                                                                const uint8_t* __restrict__ proofs, size_t n,
+                                                                uint8_t* __restrict__ okb) {
+  __shared__ uint32_t invl[GFP];
+  stage_inverses(invl);
+  const G1Ops G{invl};
+  const Pt g{vk.gx, vk.gy, vk.ginf};
+  for (size_t i = (size_t)blockIdx.x * PAIR_T + threadIdx.x; i < n; i += (size_t)gridDim.x * PAIR_T) {
+    bool ok = true;
+    Pt c{0, 0, 1};
+    uint32_t y = 0;
+    for (uint32_t j = 0; j < k; j++) {
+      const size_t e = i * k + j;
+      const Pt ci = load_g1(commits + 3 * e, ok);
+      uint32_t wi = weights[e], yi = ys[e];
+      if (wi >= HFP || yi >= HFP) {
+        ok = false;
+        wi = yi = 0;
+      }
+      c = G.add(c, G.mul(ci, wi));
+      y = (y + wi * yi % HFP) % HFP;   // hf_add(y, hf_mul(w_i, y_i))
+    }
+    const Pt w = load_g1(proofs + 3 * i, ok);
+    uint32_t z = zs[i];
+    if (z >= HFP) {
+      ok = false;
+      z = 0;
+    }
+    Pt l = G.add(c, G.negp(G.mul(g, y)));
+    l = G.add(l, G.mul(w, z));
+    const Gt lhs = pairing(G, l, vk.h1x, vk.h1y);
+    const Gt rhs = pairing(G, w, vk.hsx, vk.hsy);
+    okb[i] = (uint8_t)(!ok ? 2u : (lhs.a == rhs.a && lhs.b == rhs.b) ? 1u : 0u);
+  }
+}
+
 uint32_t blocks_for(size_t n) { return (uint32_t)std::min<size_t>((n + PAIR_T - 1) / PAIR_T, PAIR_MAX_BLOCKS); }
 
 // the checks that come before any device query
@@ -201,6 +245,20 @@ int check_vk(const char* fn, const plk_kzg_vk_t* vk, VkWords* w) {
     return PLK_ERR_ARG;
   }
   *w = VkWords{vk->g1[0], vk->g1[1], vk->g1[2], vk->g2_1[0], vk->g2_1[1], vk->g2_s[0], vk->g2_s[1]};
+  return PLK_OK;
+}
+// folded verification: k in 1 .. PLK_KZG_FOLD_MAX, then the pointers and n, the key, n k <= 2^30
+int check_fold_verify(const char* fn, const plk_kzg_vk_t* vk, int k, bool null_arg, size_t n, VkWords* w) {
+  if (k < 1 || k > PLK_KZG_FOLD_MAX) {
+    plk_set_error("%s: k = %d is outside 1 .. %d", fn, k, PLK_KZG_FOLD_MAX);
+    return PLK_ERR_ARG;
+  }
+  int rc = check_n(fn, !vk || null_arg, n);
+  if (rc || (rc = check_vk(fn, vk, w))) return rc;
+  if (n > PAIR_MAX_N / (size_t)k) {
+    plk_set_error("%s: n k = %zu x %d exceeds 2^30 entries per call", fn, n, k);
+    return PLK_ERR_RANGE;
+  }
   return PLK_OK;
 }
 
@@ -297,6 +355,39 @@ int plk_kzg_verify_batch(const plk_kzg_vk_t* vk, const uint8_t* commits3, const 
   PLK_HIP(hipMemcpy(d_z, zs, n, hipMemcpyHostToDevice));
   PLK_HIP(hipMemcpy(d_y, ys, n, hipMemcpyHostToDevice));
   if ((rc = plk_kzg_verify_batch_dev(vk, d_c, d_z, d_y, d_w, n, d_ok, nullptr))) return rc;
+  PLK_HIP(hipMemcpy(ok, d_ok, n, hipMemcpyDeviceToHost));
+  return PLK_OK;
+}
+
+int plk_kzg_verify_fold_batch_dev(const plk_kzg_vk_t* vk, int k, const uint8_t* d_commits3, const uint8_t* d_weights,
+                                  const uint8_t* d_ys, const uint8_t* d_zs, const uint8_t* d_proofs3, size_t n, uint8_t* d_ok,
+                                  void* stream) {
+  const char* fn = "plk_kzg_verify_fold_batch_dev";
+  VkWords w;
+  int rc = check_fold_verify(fn, vk, k, !d_commits3 || !d_weights || !d_ys || !d_zs || !d_proofs3 || !d_ok, n, &w);
+  if (rc || (rc = use_device())) return rc;
+  hipLaunchKernelGGL(kzg_verify_fold_kernel, dim3(blocks_for(n)), dim3(PAIR_T), 0, (hipStream_t)stream, w, (uint32_t)k,
+                     d_commits3, d_weights, d_ys, d_zs, d_proofs3, n, d_ok);
+  PLK_HIP(hipGetLastError());
+  return PLK_OK;
+}
+
+int plk_kzg_verify_fold_batch(const plk_kzg_vk_t* vk, int k, const uint8_t* commits3, const uint8_t* weights,
+                              const uint8_t* ys, const uint8_t* zs, const uint8_t* proofs3, size_t n, uint8_t* ok) {
+  const char* fn = "plk_kzg_verify_fold_batch";
+  VkWords w;
+  int rc = check_fold_verify(fn, vk, k, !commits3 || !weights || !ys || !zs || !proofs3 || !ok, n, &w);
+  if (rc || (rc = select_device())) return rc;
+  const size_t e = n * (size_t)k;   // entries
+  Scratch S;
+  if ((rc = S.alloc(fn, 5 * e + 5 * n))) return rc;
+  uint8_t *d_c = S.d, *d_wt = S.d + 3 * e, *d_y = S.d + 4 * e, *d_w = S.d + 5 * e, *d_z = d_w + 3 * n, *d_ok = d_z + n;
+  PLK_HIP(hipMemcpy(d_c, commits3, 3 * e, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_wt, weights, e, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_y, ys, e, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_w, proofs3, 3 * n, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_z, zs, n, hipMemcpyHostToDevice));
+  if ((rc = plk_kzg_verify_fold_batch_dev(vk, k, d_c, d_wt, d_y, d_z, d_w, n, d_ok, nullptr))) return rc;
   PLK_HIP(hipMemcpy(ok, d_ok, n, hipMemcpyDeviceToHost));
   return PLK_OK;
 }

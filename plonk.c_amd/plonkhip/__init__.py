@@ -107,6 +107,13 @@ SIGNATURES = {
     "plk_pairing_batch_dev": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
     "plk_kzg_verify_batch": (C.c_int, [_vp, _u8p, _u8p, _u8p, _u8p, _sz, _u8p]),
     "plk_kzg_verify_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "plk_kzg_fold_workspace": (_sz, [C.POINTER(_sz), C.POINTER(C.c_int), C.c_int]),
+    "plk_kzg_open_fold_batch": (C.c_int, [_vp, C.POINTER(_u8p), C.POINTER(_sz), _u8p, C.POINTER(C.c_int), _u8p,
+                                          C.c_int, _u8p, _u8p]),
+    "plk_kzg_open_fold_batch_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _u8p, C.POINTER(C.c_int), _u8p,
+                                              C.c_int, _vp, _vp, C.POINTER(_vp), _vp, _vp]),
+    "plk_kzg_verify_fold_batch": (C.c_int, [_vp, C.c_int, _u8p, _u8p, _u8p, _u8p, _u8p, _sz, _u8p]),
+    "plk_kzg_verify_fold_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
 }
 
 # PLK_OPT_* (include/plonkhip.h), by the name without the prefix
@@ -647,6 +654,83 @@ def kzg_verify_dev(vk, commits, zs, ys, proofs, n, ok, stream=None):
     """vk: a KzgVk on the host; the rest device tensors (or raw pointers) of any alignment; ok: n bytes"""
     _check("plk_kzg_verify_batch_dev", lib().plk_kzg_verify_batch_dev(
         C.byref(vk), _ptr(commits), _ptr(zs), _ptr(ys), _ptr(proofs), int(n), _ptr(ok), _stream(stream)))
+
+
+# ---------------------------------------------------------------- KZG folded openings
+def _fold_start(counts):
+    start = [0]
+    for k in counts:
+        start.append(start[-1] + int(k))
+    return (C.c_int * len(start))(*start)
+
+
+def kzg_fold_workspace(lens, start):
+    """plk_kzg_fold_workspace: bytes of d_work for kzg_open_fold_dev; start: the ngroups + 1 group
+    boundaries in the flat arrays.  No device needed; 0 for bad arguments."""
+    ng = len(start) - 1
+    ls = (_sz * max(len(lens), 1))(*[int(v) for v in lens])
+    st = (C.c_int * max(len(start), 1))(*[int(v) for v in start])
+    return int(lib().plk_kzg_fold_workspace(ls, st, ng))
+
+
+def kzg_open_fold(srs, groups, weights, zs):
+    """plk_kzg_open_fold_batch: groups = [[polynomial, ...], ...] (1 .. 16 each), weights the same shape,
+    one z per group -> ([[y, ...], ...], [proof 3 bytes per group]): every y_i = p_i(z) and the commitment
+    of (sum_i w_i (p_i - y_i)) / (x - z)"""
+    if len(weights) != len(groups) or any(len(w) != len(g) for w, g in zip(weights, groups)):
+        raise ValueError("one weight per polynomial")
+    arrs, ptrs, lens, n = _host_polys([p for g in groups for p in g])
+    wa = _u8([w for g in weights for w in g]).reshape(-1)
+    za = _u8(zs).reshape(-1)
+    ng = len(groups)
+    if za.size != ng:
+        raise ValueError("one z per group")
+    start = _fold_start(len(g) for g in groups)
+    ys = np.zeros(max(n, 1), np.uint8)
+    out = np.zeros(3 * max(ng, 1), np.uint8)
+    _check("plk_kzg_open_fold_batch", lib().plk_kzg_open_fold_batch(_srs_h(srs), ptrs, lens, _p(wa), start, _p(za), ng,
+                                                                    _p(ys), _p(out)))
+    return ([[int(v) for v in ys[start[g]:start[g + 1]]] for g in range(ng)],
+            [bytes(out[3 * g:3 * g + 3]) for g in range(ng)])
+
+
+def kzg_open_fold_dev(srs, polys, lens, weights, start, zs, ys, res, quots=None, work=None, stream=None):
+    """polys: the flat list of device tensors (or raw pointers), group g = [start[g], start[g + 1]); lens,
+    weights, start, zs: host values; ys: len(polys) device bytes; res: one zeroed record per group;
+    quots: None, or per group None / max(L - 1, 1) device bytes; work: kzg_fold_workspace(lens, start)
+    device bytes."""
+    n = len(polys)
+    ng = len(start) - 1
+    ptrs = (_vp * max(n, 1))(*[_ptr(p) for p in polys])
+    ls = (_sz * max(n, 1))(*[int(v) for v in lens])
+    st = (C.c_int * max(len(start), 1))(*[int(v) for v in start])
+    wa = _u8(weights).reshape(-1)
+    za = _u8(zs).reshape(-1)
+    qs = None if quots is None else (_vp * max(ng, 1))(*[_ptr(q) for q in quots])
+    _check("plk_kzg_open_fold_batch_dev", lib().plk_kzg_open_fold_batch_dev(
+        _srs_h(srs), ptrs, ls, _p(wa), st, _p(za), ng, _ptr(ys), _ptr(res), qs, _ptr(work), _stream(stream)))
+
+
+def kzg_verify_fold(vk, k, commits, weights, ys, zs, proofs):
+    """plk_kzg_verify_fold_batch: job b owns entries [k b, k (b + 1)) of commits (3 bytes each), weights
+    and ys; one z and one proof per job -> n bytes, 1 accept / 0 reject / 2 an invalid byte in the job"""
+    c, w = _u8(commits).reshape(-1), _u8(proofs).reshape(-1)
+    wa, ya, za = _u8(weights).reshape(-1), _u8(ys).reshape(-1), _u8(zs).reshape(-1)
+    n = za.size
+    e = n * int(k)
+    if c.size != 3 * e or wa.size != e or ya.size != e or w.size != 3 * n:
+        raise ValueError("n k commitments, weights and ys; n zs and proofs")
+    ok = np.zeros(max(n, 1), np.uint8)
+    _check("plk_kzg_verify_fold_batch", lib().plk_kzg_verify_fold_batch(C.byref(vk), int(k), _p(c), _p(wa), _p(ya),
+                                                                        _p(za), _p(w), n, _p(ok)))
+    return ok[:n]
+
+
+def kzg_verify_fold_dev(vk, k, commits, weights, ys, zs, proofs, n, ok, stream=None):
+    """vk: a KzgVk on the host; the rest device tensors (or raw pointers) of any alignment; ok: n bytes"""
+    _check("plk_kzg_verify_fold_batch_dev", lib().plk_kzg_verify_fold_batch_dev(
+        C.byref(vk), int(k), _ptr(commits), _ptr(weights), _ptr(ys), _ptr(zs), _ptr(proofs), int(n), _ptr(ok),
+        _stream(stream)))
 
 
 # ---------------------------------------------------------------- device prover
