@@ -134,12 +134,17 @@ class Prover:
         for cp in copies:
             s = []
             for t, idx in cp:
-                if t not in (0, 1, 2):
+                # An index outside 1..n is read out of bounds by the reference (undefined there); the
+                # device defines it as the COPY exit (include/plonkhip.h, "bad copy"), and so does this.
+                if t not in (0, 1, 2) or not 1 <= idx <= n:
                     raise ProveError("Invalid copy_of type")
                 s.append(int(roots[t][idx - 1]))
             sig.append(s)
         f = [self.interpolate(x) for x in (a, b, c, q_o, q_m, q_l, q_r, q_c, sig[0], sig[1], sig[2])]
         s1, s2, s3 = f[8], f[9], f[10]
+        # round 1's commitments come before the grand product (src/plonk.h:299-301): on a short SRS
+        # their exit is taken before the acc_x assert can fail
+        self.round1(f[0], f[1], f[2], rnd)
         # round 2 grand product src/plonk.h:326-359
         al, be, ga = chal[0] % P, chal[1] % P, chal[2] % P
         acc = [1]
@@ -158,6 +163,15 @@ class Prover:
         l_1 = self.interpolate(e0)
         return self.rounds(f + [acc_x, l_1], chal, rnd, strict=True)
 
+    # -- src/plonk.h:277-301 -----------------------------------------------------------------
+    def round1(self, fa, fb, fc, rnd):
+        b1, b2, b3, b4, b5, b6 = (x % P for x in rnd[:6])
+        zh = self.z_h
+        a_x = poly_add(self.mul(_trim([b2, b1]), zh), _trim(fa))
+        b_x = poly_add(self.mul(_trim([b4, b3]), zh), _trim(fb))
+        c_x = poly_add(self.mul(_trim([b6, b5]), zh), _trim(fc))
+        return a_x, b_x, c_x, self.commit(a_x), self.commit(b_x), self.commit(c_x)
+
     # -- src/plonk.h:277-655 -----------------------------------------------------------------
     def rounds(self, polys, chal, rnd, strict=True):
         n = self.n
@@ -166,10 +180,7 @@ class Prover:
         b1, b2, b3, b4, b5, b6, b7, b8, b9 = (x % P for x in rnd)
         zh = self.z_h
         # round 1
-        a_x = poly_add(self.mul(_trim([b2, b1]), zh), fa)
-        b_x = poly_add(self.mul(_trim([b4, b3]), zh), fb)
-        c_x = poly_add(self.mul(_trim([b6, b5]), zh), fc)
-        a_s, b_s, c_s = self.commit(a_x), self.commit(b_x), self.commit(c_x)
+        a_x, b_x, c_x, a_s, b_s, c_s = self.round1(fa, fb, fc, rnd)
         # round 2 (acc_x given)
         z_x = poly_add(self.mul(_trim([b9, b8, b7]), zh), acc_x)
         z_s = self.commit(z_x)

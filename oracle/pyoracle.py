@@ -246,6 +246,49 @@ class Reference(_Lib):
         return {"h": bytes(h), "k1_h": bytes(k1), "k2_h": bytes(k2), "h_pows_inv": bytes(hinv),
                 "z_h": bytes(zh[:zl]), "g1s": bytes(g1s)}
 
+    # exits of ref_prove_n by number (ref_harness.c REF_X_*; the numbers of plonkhip.h's batch status word)
+    EXITS = (None, "GATE", "COPY", "SRS", "ACC", "REM_T", "SLICE", "REM_W1", "REM_W2")
+
+    def plonk_data(self, n, secret=2, srs_n=6, srs_mode=0):
+        """plonk4_data for plonk_new(srs, n), n in 1..16"""
+        f = self.lib.ref_plonk_data
+        f.restype = C.c_size_t
+        f.argtypes = [C.c_size_t, C.c_uint8, C.c_size_t, C.c_int] + [_u8p] * 6
+        h, k1, k2 = (np.zeros(n, np.uint8) for _ in range(3))
+        hinv = np.zeros(n * n, np.uint8)
+        zh = np.zeros(n + 1, np.uint8)
+        g1s = np.zeros(3 * (srs_n + 1), np.uint8)
+        zl = f(n, secret, srs_n, srs_mode, _ptr(h), _ptr(k1), _ptr(k2), _ptr(hinv), _ptr(zh), _ptr(g1s))
+        return {"h": bytes(h), "k1_h": bytes(k1), "k2_h": bytes(k2), "h_pows_inv": bytes(hinv),
+                "z_h": bytes(zh[:zl]), "g1s": bytes(g1s)}
+
+    def prove_n(self, n, gates, copies, wires, chal, rnd, secret=2, srs_n=6, srs_mode=0):
+        """(proof bytes, None, None) or (None, exit name of EXITS, gate index or None); a child that ended
+        in no exit the reference names is an error of the caller's inputs"""
+        f = self.lib.ref_prove_n
+        f.restype = C.c_int
+        f.argtypes = [C.c_size_t] + [_u8p] * 5 + [C.c_uint8, C.c_size_t, C.c_int, _u8p, C.POINTER(C.c_int)]
+        gates, copies, wires, chal, rnd = _u8(gates), _u8(copies), _u8(wires), _u8(chal), _u8(rnd)
+        assert (gates.size, copies.size, wires.size, chal.size, rnd.size) == (5 * n, 6 * n, 3 * n, 5, 9)
+        out = np.zeros(34, np.uint8)
+        kind = (C.c_int * 2)()
+        rc = f(n, _ptr(gates), _ptr(copies), _ptr(wires), _ptr(chal), _ptr(rnd), secret, srs_n, srs_mode,
+               _ptr(out), kind)
+        if rc == 0:
+            return bytes(out), None, None
+        if rc < 0 or rc != kind[0] or rc >= len(self.EXITS):
+            raise RuntimeError("ref_prove_n: the reference ended without one of its named exits (n = %d)" % n)
+        return None, self.EXITS[rc], kind[1] if rc == 1 else None
+
+    @staticmethod
+    def has_generic(path=os.path.join(HERE, "_ref", "libplonkref.so")):
+        """whether the library is there and has ref_plonk_data / ref_prove_n (one built from an older
+        ref_harness.c, kept where the reference's sources are absent, has not)"""
+        if not os.path.exists(path):
+            return False
+        lib = C.CDLL(path)
+        return all(hasattr(lib, f) for f in ("ref_plonk_data", "ref_prove_n"))
+
     @staticmethod
     def available(path=os.path.join(HERE, "_ref", "libplonkref.so")):
         return os.path.exists(path)

@@ -20,12 +20,16 @@
  *   ref_interpolate4  -> plonk_new + interpolate_at_h                   src/plonk.h:53,162
  *   ref_prove4        -> srs_create + plonk_new + plonk_prove           src/srs.h:18, src/plonk.h:53,223
  *   ref_plonk4_data   -> srs_create + plonk_new: h, k1_h, k2_h, h_pows_inv, z_h_x, g1s
+ *   ref_plonk_data    -> the same for plonk_new(srs, n), any n the reference's H supports (1..16)
+ *   ref_prove_n       -> srs_create + plonk_new(srs, n) + plonk_prove; names the exit it took
  *
  * The same file compiled with `-include include/prelude.h -DPLK_NO_FORK` (target
  * _ref/libplonkref_dropin.so) is the DROP-IN demonstration: the reference's unmodified
  * plonk.h prover, with poly_mul / srs_eval_at_s resolved to libplonkhip (GPU).
  */
+#include <signal.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -257,3 +261,144 @@ int ref_prove4(const uint8_t *gates, const uint8_t *copies, const uint8_t *wires
   return 0;
 #endif
 }
+
+/* ref_plonk4_data for plonk_new(srs, n): h, k1_h, k2_h (n each), h_pows_inv row-major (n * n),
+ * z_h_x (returns its length, at most n + 1), g1s (3 * (srs_n + 1) bytes). */
+size_t ref_plonk_data(size_t n, uint8_t secret, size_t srs_n, int srs_mode, uint8_t *h, uint8_t *k1,
+                      uint8_t *k2, uint8_t *hinv, uint8_t *zh, uint8_t *g1s) {
+  SRS srs = make_srs(secret, srs_n, srs_mode);
+  memcpy(g1s, srs.g1s, 3 * srs.len);
+  PLONK plonk = plonk_new(srs, n);
+  for (size_t i = 0; i < n; i++) {
+    h[i] = plonk.h[i].value;
+    k1[i] = plonk.k1_h[i].value;
+    k2[i] = plonk.k2_h[i].value;
+    for (size_t c = 0; c < n; c++) hinv[n * i + c] = matrix_get(&plonk.h_pows_inv, i, c).value;
+  }
+  size_t zl = plonk.z_h_x.len;
+  memcpy(zh, plonk.z_h_x.coeffs, zl);
+  plonk_free(&plonk);
+  return zl;
+}
+
+#ifndef PLK_NO_FORK
+/*
+ * One n-gate prove through the reference plonk_prove in a forked child, as ref_prove4, with the
+ * child's stdout and stderr captured so that a rejection is named by the reference's own text:
+ *   gates 5n: q_m | q_l | q_r | q_o | q_c     copies 6n: c_a | c_b | c_c as (type, index) pairs
+ *   wires 3n: a | b | c                       chal 5, rnd 9, secret / srs_n / srs_mode as ref_prove4
+ * Returns 0 and fills out[34] for a proof; otherwise the kind of the exit, also in kind[0], with
+ * the index of the unsatisfied gate in kind[1] for REF_X_GATE.  Returns -1 where the child ended
+ * with a text that is none of these, or without one (a fault of the caller's inputs, not a
+ * ninth kind), and for a copy of type 0..2 whose index is not in 1..n, which the reference
+ * would read out of bounds.
+ */
+enum { REF_X_GATE = 1, REF_X_COPY, REF_X_SRS, REF_X_ACC, REF_X_REM_T, REF_X_SLICE, REF_X_REM_W1, REF_X_REM_W2 };
+
+static void prove_n_body(size_t n, const uint8_t *gates, const uint8_t *copies, const uint8_t *wires,
+                         const uint8_t *chal, const uint8_t *rnd, uint8_t secret, size_t srs_n,
+                         int srs_mode, uint8_t *buf) {
+  SRS srs = make_srs(secret, srs_n, srs_mode);
+  PLONK plonk = plonk_new(srs, n);
+  CONSTRAINTS c;
+  memset(&c, 0, sizeof c);
+  c.num_constraints = n;
+  c.num_gates = n;
+  HF *q[5];
+  for (int k = 0; k < 5; k++) {
+    q[k] = malloc(n);
+    memcpy(q[k], gates + n * k, n);
+  }
+  c.q_m = q[0]; c.q_l = q[1]; c.q_r = q[2]; c.q_o = q[3]; c.q_c = q[4];
+  COPY_OF *cp[3];
+  for (int k = 0; k < 3; k++) {
+    cp[k] = malloc(n * sizeof(COPY_OF));
+    for (size_t i = 0; i < n; i++) {
+      cp[k][i].type = (COPY_OF_TYPE)copies[2 * n * k + 2 * i];
+      cp[k][i].index = copies[2 * n * k + 2 * i + 1];
+    }
+  }
+  c.c_a = cp[0]; c.c_b = cp[1]; c.c_c = cp[2];
+  ASSIGNMENTS as;
+  as.len = n;
+  as.a = malloc(n); as.b = malloc(n); as.c = malloc(n);
+  memcpy(as.a, wires, n); memcpy(as.b, wires + n, n); memcpy(as.c, wires + 2 * n, n);
+  CHALLENGE ch = {{chal[0]}, {chal[1]}, {chal[2]}, {chal[3]}, {chal[4]}};
+  HF r9[9];
+  memcpy(r9, rnd, 9);
+  PROOF p = plonk_prove(&plonk, &c, &as, &ch, r9);
+  memcpy(buf, &p, 34);
+}
+
+static size_t read_all(int fd, char *buf, size_t cap) {
+  size_t got = 0;
+  while (got < cap) {
+    ssize_t k = read(fd, buf + got, cap - got);
+    if (k <= 0) break;
+    got += (size_t)k;
+  }
+  return got;
+}
+
+int ref_prove_n(size_t n, const uint8_t *gates, const uint8_t *copies, const uint8_t *wires,
+                const uint8_t *chal, const uint8_t *rnd, uint8_t secret, size_t srs_n, int srs_mode,
+                uint8_t *out, int *kind) {
+  kind[0] = kind[1] = 0;
+  if (n < 1 || n > 16) return -1;
+  for (size_t i = 0; i < 3 * n; i++)
+    if (copies[2 * i] <= 2 && (copies[2 * i + 1] < 1 || copies[2 * i + 1] > n)) return -1;
+  int pfd[2], tfd[2];
+  if (pipe(pfd) != 0) return -1;
+  if (pipe(tfd) != 0) { close(pfd[0]); close(pfd[1]); return -1; }
+  fflush(stdout);
+  fflush(stderr);
+  pid_t pid = fork();
+  if (pid < 0) { close(pfd[0]); close(pfd[1]); close(tfd[0]); close(tfd[1]); return -1; }
+  if (pid == 0) {
+    close(pfd[0]);
+    close(tfd[0]);
+    dup2(tfd[1], 1);
+    dup2(tfd[1], 2);
+    setvbuf(stdout, NULL, _IONBF, 0);
+    signal(SIGABRT, SIG_DFL);   /* a failed assert ends the child; no handler of the host process runs */
+    uint8_t buf[34];
+    prove_n_body(n, gates, copies, wires, chal, rnd, secret, srs_n, srs_mode, buf);
+    ssize_t w = write(pfd[1], buf, 34);
+    _exit(w == 34 ? 0 : 3);
+  }
+  close(pfd[1]);
+  close(tfd[1]);
+  uint8_t buf[34];
+  char text[2048];
+  size_t got = read_all(pfd[0], (char *)buf, 34);
+  size_t tl = read_all(tfd[0], text, sizeof text - 1);
+  text[tl] = 0;
+  close(pfd[0]);
+  close(tfd[0]);
+  int status = 0;
+  waitpid(pid, &status, 0);
+  if (WIFEXITED(status) && WEXITSTATUS(status) == 0) {
+    if (got != 34 || tl != 0) return -1;
+    memcpy(out, buf, 34);
+    return 0;
+  }
+  const int aborted = WIFSIGNALED(status) && WTERMSIG(status) == SIGABRT;
+  const int exited = WIFEXITED(status) && WEXITSTATUS(status) == EXIT_FAILURE;
+  size_t gate = 0;
+  const char *g = strstr(text, "Constraint ");
+  int k = 0;
+  if (g && sscanf(g, "Constraint %zu not satisfied.", &gate) == 1 && strstr(text, "constraints_satisfy(") && aborted)
+    k = REF_X_GATE;
+  else if (strstr(text, "Invalid copy_of type") && exited) k = REF_X_COPY;
+  else if (strstr(text, "Poynomial degree exceeds SRS size") && exited) k = REF_X_SRS;
+  else if (strstr(text, "hf_equal(acc_x_eval, hf_one())") && aborted) k = REF_X_ACC;
+  else if (strstr(text, "Non-zero remainder in t(x) division") && exited) k = REF_X_REM_T;
+  else if (strstr(text, "Invalid slice indices in poly_slice") && exited) k = REF_X_SLICE;
+  else if (strstr(text, "poly_is_zero(&rem1)") && aborted) k = REF_X_REM_W1;
+  else if (strstr(text, "poly_is_zero(&rem2)") && aborted) k = REF_X_REM_W2;
+  if (!k) return -1;
+  kind[0] = k;
+  kind[1] = (int)gate;
+  return k;
+}
+#endif

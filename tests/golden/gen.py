@@ -83,6 +83,128 @@ def digest(c):
     return hashlib.sha256(np.asarray(c, dtype=np.uint8).tobytes()).hexdigest()
 
 
+CIRCUIT_KINDS = ("identity", "respect17", "respect3", "perm", "map", "degenerate", "mixed",
+                 "gate", "gate2", "gate_last", "copy3", "copy255", "copy_gate")
+
+
+def _draw(r, count, modulus):
+    """the next `count` values of the stream r (a list holding one array) reduced mod `modulus`"""
+    out = (r[0][:count] % np.uint64(modulus)).astype(np.int64)
+    r[0] = r[0][count:]
+    return out
+
+
+def _shuffle(r, items):
+    """a uniform permutation of `items`: ordered by fresh 64-bit keys (stable, so bit-exact anywhere)"""
+    keys = r[0][:len(items)]
+    r[0] = r[0][len(items):]
+    return [items[i] for i in np.argsort(keys, kind="stable")]
+
+
+def prove_circuit(n, kind, seed):
+    """One n-gate circuit with challenges and blinding, a pure function of (n, kind, seed): the dict of
+    tests/golden/prove.json's cases (gates 5n: q_m q_l q_r q_o q_c; copies 6n: c_a c_b c_c as (type, index)
+    pairs; wires 3n: a b c; chal 5; rand 9).  All bytes canonical (< 17, copy types 0-2 except where the kind
+    says otherwise, copy indices 1..n).  Every gate holds by construction: selectors, a and b random, c solved
+    through q_o where q_o != 0 and q_c solved otherwise.
+
+    kind (one of CIRCUIT_KINDS, optionally followed by "+b1" for a blinding scalar b1 != 0 and plain challenges):
+      identity   every wire slot its own copy
+      respect17  a random permutation inside each class of equal wire values over all 3n slots, wires from 17 values
+      respect3   the same with a, b and the free c from 3 values: large classes that cross columns
+      perm       an arbitrary permutation of the 3n slots
+      map        an arbitrary map of the 3n slots (not injective)
+      degenerate zero selectors, constant wires, identity copies, beta = 0 in half the draws
+      mixed      zero selectors, wires constant per column, identity or value-respecting copies
+      gate / gate2 / gate_last   "respect17" with one wire c changed at a random gate / at two gates / at gate n - 1
+      copy3 / copy255 / copy_gate  "respect17" with one copy type set to 3 / to 255 / to 3 and one gate failing too
+    Challenges and blinding are uniform, with beta = 0, gamma = 0, beta = gamma = 0, b7 = b8 = b9 = 0 and all
+    blinding zero each mixed in at one draw in sixteen."""
+    base, _, mod = kind.partition("+")
+    assert mod in ("", "b1") and 1 <= n <= 16
+    r = [splitmix64(int(seed) * 1000003 + 4099 * n + CIRCUIT_KINDS.index(base), 16 * n + 64)]
+    p = 17
+    sel = _draw(r, 5 * n, p).reshape(5, n)
+    q_m, q_l, q_r, q_o, q_c = sel
+    vals = 3 if base == "respect3" else p
+    a, b, c = _draw(r, 3 * n, vals).reshape(3, n)
+    if vals == 3:                                   # three values spread over the field, not 0 1 2
+        spread = _draw(r, 3, p)
+        a, b, c = spread[a], spread[b], spread[c]
+    else:
+        _draw(r, 3, p)
+    if base in ("degenerate", "mixed"):
+        sel[:] = 0
+        col = _draw(r, 3, p)
+        if base == "degenerate":
+            col[:] = col[0]
+        a, b, c = (np.full(n, v, np.int64) for v in col)
+    else:
+        _draw(r, 3, p)
+    rest = (q_l * a + q_r * b + q_m * (a * b % p)) % p
+    for i in range(n):
+        if q_o[i]:
+            c[i] = (p - (rest[i] + q_c[i]) % p) * pow(int(q_o[i]), p - 2, p) % p
+        else:
+            q_c[i] = (p - rest[i]) % p
+    wires = np.concatenate([a, b, c])
+    slots = list(range(3 * n))
+    how = {"identity": "identity", "degenerate": "identity", "perm": "perm", "map": "map"}.get(base, "respect")
+    pick = _draw(r, 1, 2)[0]
+    if base == "mixed" and pick:
+        how = "identity"
+    if how == "identity":
+        _shuffle(r, slots)
+        target = slots
+    elif how == "perm":
+        target = _shuffle(r, slots)
+    elif how == "map":
+        target = [int(x) for x in _draw(r, 3 * n, 3 * n)]
+    else:
+        order = _shuffle(r, slots)                  # class members in a random order: source -> next member
+        target = list(slots)
+        for v in range(p):
+            cls = [s for s in slots if wires[s] == v]
+            img = [s for s in order if wires[s] == v]
+            for s, t in zip(cls, img):
+                target[s] = t
+    copies = [x for t in target for x in (t // n, t % n + 1)]
+    extra = _draw(r, 8, 1 << 30)
+    wires = [int(x) for x in wires]
+    if base in ("gate", "gate2", "gate_last", "copy_gate"):
+        g = n - 1 if base == "gate_last" else int(extra[0] % n)
+        hit = {g, int(extra[1] % n)} if base == "gate2" else {g}
+        for i in hit:                               # the changed c must count: q_o = 1 at that gate, c off by 1..16
+            sel[3][i] = 1
+            wires[2 * n + i] = int((p - (rest[i] + q_c[i]) % p) % p + 1 + extra[2] % 16) % p
+    if base in ("copy3", "copy255", "copy_gate"):
+        copies[2 * int(extra[3] % (3 * n))] = 255 if base == "copy255" else 3
+    chal = [int(x) for x in _draw(r, 5, p)]
+    rand = [int(x) for x in _draw(r, 9, p)]
+    variant = int(_draw(r, 1, 16)[0])
+    if mod == "b1":
+        rand[0] = 1 + rand[0] % 16
+    elif base == "degenerate":
+        if variant < 8:
+            chal[1] = 0
+    elif variant == 0:
+        chal[1] = 0
+    elif variant == 1:
+        chal[2] = 0
+    elif variant == 2:
+        chal[1] = chal[2] = 0
+    elif variant == 3:
+        rand[6] = rand[7] = rand[8] = 0
+    elif variant == 4:
+        rand = [0] * 9
+    return {"gates": [int(x) for x in sel.reshape(-1)], "copies": copies, "wires": wires, "chal": chal, "rand": rand}
+
+
+def circuit_bytes(c):
+    """the 14n bytes of one prove_batch entry: q_m q_l q_r q_o q_c | copy_a copy_b copy_c | a b c"""
+    return bytes(c["gates"]) + bytes(c["copies"]) + bytes(c["wires"])
+
+
 def prove_instance(n, seed, srs_len):
     """Prove-shaped synthetic instance (rounds 1-5 at n gates): 13 random 'interpolated'
     polynomials of length n, challenges / blinding scalars, Z_H = x^n - 1, an SRS over the whole
