@@ -452,7 +452,13 @@ int plk_kzg_verify_fold_batch_dev(const plk_kzg_vk_t *vk /* HOST */, int k, cons
  * circuit tables h, k1_h, k2_h, h_pows_inv are optional (needed only by plk_prover_prove).
  * h_pows_inv is the inverse Vandermonde matrix row-major, [r * n + c] = matrix_get(r, c).
  * A prover owns its stream and work buffers: one call at a time per plk_prover_t (distinct
- * provers may run from different threads). */
+ * provers may run from different threads).
+ * Largest n: with a binomial Z_H (x^n - 1) a proof needs n <= 3,932,158.  Round 3's products run as
+ * one exact transform each, over F29 or, past its range, BabyBear (p = 15 2^27 + 1), which holds a
+ * product of bytes < 17 exactly while 256 min(la, lb) < p; t_2 = (A2 B2)(C2 z) has a shorter operand
+ * of 2n + 3 coefficients, and (2n + 3) 256 < p gives the limit.  plk_prover_create accepts a larger
+ * n; plk_prover_prove / plk_prover_rounds_dev then return PLK_ERR_RANGE ("outside the exact range")
+ * before that batch's transforms are launched, and the prover can still be destroyed. */
 typedef struct plk_prover plk_prover_t;
 typedef struct {
   size_t n;                                  /* gates = |H| */
