@@ -287,6 +287,58 @@ int plk_matrix_inv(const uint8_t *mat, size_t n, uint8_t *out);
  * poly_new; out holds n bytes. */
 int plk_interpolate(const uint8_t *h_pows_inv, const uint8_t *values, size_t n, uint8_t *out, size_t *out_len);
 
+/* ---- poly linear combinations: add, sub, scale, negate, shift, twist in one pass ---------
+ * The reference's elementwise polynomial ops (src/poly.h:66-104, 179-216, 240-254: poly_add_hf, poly_add,
+ * poly_sub, poly_scale, poly_shift, poly_negate; poly_slice is p + start, end - start) and the x -> omega x
+ * coefficient loop of src/plonk.h:466-470, composed over up to PLK_LC_MAX_TERMS polynomials in one pass
+ * over device buffers: with these the _dev entry points are closed under the operations of a KZG / PLONK
+ * round (tests/test_public_api_prove_gpu.py rebuilds a whole proof from them).
+ *
+ * Semantics (the specification).  Each term is transformed in the order twist -> scale -> negate -> shift;
+ * the accumulator starts as term 0 transformed; every later term is folded in, in order, with the
+ * reference's poly_add or poly_sub; poly_add_hf is applied last, to coefficient 0.  Per coefficient j < L
+ * = max_i(len_i + shift_i): the byte formulas are the reference's own hf_add, hf_sub, hf_neg, hf_mul with
+ * their uint8_t / int8_t behaviour on bytes >= 17; a term contributes hf_zero() outside
+ * [shift, shift + len) and the operation is still applied there (as poly_add does for i >= len).  The
+ * reference trims intermediate results; those trims change no byte (past a trimmed length both operands
+ * read as zero), so out is the untrimmed result over L bytes, exact for EVERY input byte value.
+ * d_nz[b] receives the index + 1 of the last non-zero byte of job b (0: all zero) -- the convention of
+ * plk_poly_mul_dev -- and needs no initialisation by the caller.
+ * Aliasing: out may be exactly a term's p when that term's shift is 0 (accumulation in place).  Any other
+ * overlap of an output with any job's input, or with another output, of the same call is the caller's
+ * error.
+ * Batch: any n; a launch carries whole jobs up to a fixed number of jobs and terms, larger batches run as
+ * consecutive launches on the stream.  The call needs no workspace and keeps no state; pointers may have
+ * any alignment (16-byte aligned ones run fastest).  Calls on different streams may run concurrently.
+ * Errors (all checked before any device query): a NULL pointer, n <= 0, nterms outside
+ * 1 .. PLK_LC_MAX_TERMS, len == 0, sub or neg > 1, scale in 17 .. 254, twist > 16, add_hf outside -1 .. 16
+ * or term 0 with sub = 1 are PLK_ERR_ARG; L >= 2^32 is PLK_ERR_RANGE.  No GPU is PLK_ERR_NODEV -- there is
+ * no CPU fallback.  The device rules are those of plk_kzg_verify_batch(_dev). */
+#define PLK_LC_MAX_TERMS 16
+#define PLK_LC_RAW 0xFF
+typedef struct {
+  const uint8_t *p;   /* coefficients (device pointer in the _dev form) */
+  size_t len;         /* >= 1 */
+  size_t shift;       /* poly_shift: coefficient i lands at i + shift */
+  uint8_t sub;        /* 0: folded in with poly_add, 1: with poly_sub (term 0: must be 0) */
+  uint8_t scale;      /* 0..16: poly_scale by it (hf_mul per byte; 0 gives poly_zero);
+                         PLK_LC_RAW: the bytes as they are */
+  uint8_t neg;        /* 1: poly_negate (hf_neg per byte) */
+  uint8_t twist;      /* 0: none; 1..16: coefficient i becomes hf_mul(p[i], hf_pow(twist, i)),
+                         the x -> twist*x substitution of src/plonk.h:466-470 */
+} plk_lc_term_t;
+typedef struct {
+  const plk_lc_term_t *terms;   /* HOST array, 1..PLK_LC_MAX_TERMS */
+  int nterms;
+  int add_hf;                   /* -1: none; 0..16: poly_add_hf(result, add_hf) at the end */
+  uint8_t *out;                 /* L = max_i(len_i + shift_i) bytes, every one written */
+} plk_lc_job_t;
+size_t plk_poly_lincomb_len(const plk_lc_job_t *job);            /* L; host only; 0 for bad arguments */
+int plk_poly_lincomb(const plk_lc_job_t *job, size_t *out_len);  /* host buffers, synchronous;
+                                                                    *out_len trimmed as poly_new, >= 1 */
+int plk_poly_lincomb_batch_dev(const plk_lc_job_t *jobs, int n, uint32_t *d_nz /* n words or NULL */,
+                               void *stream);
+
 /* ---- KZG over a resident SRS: commit and open, batched ----------------------------------
  * The commitment (srs_eval_at_s, src/srs.h:53-68) and the opening the reference spells out twice per
  * proof (src/plonk.h:606-621: y = p(z), q = (p - y) / (x - z), [q]) against an SRS that stays on the

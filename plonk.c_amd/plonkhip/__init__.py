@@ -114,6 +114,9 @@ SIGNATURES = {
                                               C.c_int, _vp, _vp, C.POINTER(_vp), _vp, _vp]),
     "plk_kzg_verify_fold_batch": (C.c_int, [_vp, C.c_int, _u8p, _u8p, _u8p, _u8p, _u8p, _sz, _u8p]),
     "plk_kzg_verify_fold_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "plk_poly_lincomb_len": (_sz, [_vp]),
+    "plk_poly_lincomb": (C.c_int, [_vp, C.POINTER(_sz)]),
+    "plk_poly_lincomb_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
 }
 
 # PLK_OPT_* (include/plonkhip.h), by the name without the prefix
@@ -731,6 +734,78 @@ def kzg_verify_fold_dev(vk, k, commits, weights, ys, zs, proofs, n, ok, stream=N
     _check("plk_kzg_verify_fold_batch_dev", lib().plk_kzg_verify_fold_batch_dev(
         C.byref(vk), int(k), _ptr(commits), _ptr(weights), _ptr(ys), _ptr(zs), _ptr(proofs), int(n), _ptr(ok),
         _stream(stream)))
+
+
+# ---------------------------------------------------------------- poly linear combinations
+PLK_LC_MAX_TERMS = 16
+PLK_LC_RAW = 0xFF
+
+
+class LcTerm(C.Structure):
+    """plk_lc_term_t"""
+    _fields_ = [("p", C.c_void_p), ("len", _sz), ("shift", _sz), ("sub", C.c_uint8), ("scale", C.c_uint8),
+                ("neg", C.c_uint8), ("twist", C.c_uint8)]
+
+
+class LcJob(C.Structure):
+    """plk_lc_job_t"""
+    _fields_ = [("terms", C.POINTER(LcTerm)), ("nterms", C.c_int), ("add_hf", C.c_int), ("out", C.c_void_p)]
+
+
+def lc_term(p, len=None, shift=0, sub=0, scale=PLK_LC_RAW, neg=0, twist=0):
+    """one term of a linear combination as a dict; p: bytes / array (host form) or a device tensor / raw
+    pointer (_dev form, len then required unless p is a tensor)"""
+    return {"p": p, "len": len, "shift": shift, "sub": sub, "scale": scale, "neg": neg, "twist": twist}
+
+
+def _lc_job(terms, add_hf, out, keep, host):
+    arr = (LcTerm * max(len(terms), 1))()
+    for i, t in enumerate(terms):
+        p, ln = t["p"], t.get("len")
+        if host:
+            a = _u8(p).reshape(-1)
+            keep.append(a)
+            ptr, ln = a.ctypes.data, a.size if ln is None else ln
+        else:
+            ptr, ln = _ptr(p), p.numel() if ln is None else ln
+        arr[i] = LcTerm(ptr, int(ln), int(t.get("shift", 0)), int(t.get("sub", 0)), int(t.get("scale", PLK_LC_RAW)),
+                        int(t.get("neg", 0)), int(t.get("twist", 0)))
+    keep.append(arr)
+    return LcJob(arr, len(terms), -1 if add_hf is None else int(add_hf), out)
+
+
+def poly_lincomb_len(terms, add_hf=None):
+    """plk_poly_lincomb_len: L = max(len + shift) over lc_term dicts whose p may be None; 0 for bad
+    arguments.  No device needed."""
+    arr = (LcTerm * max(len(terms), 1))()
+    for i, t in enumerate(terms):
+        arr[i] = LcTerm(1, int(t["len"]), int(t.get("shift", 0)), int(t.get("sub", 0)),
+                        int(t.get("scale", PLK_LC_RAW)), int(t.get("neg", 0)), int(t.get("twist", 0)))
+    job = LcJob(arr, len(terms), -1 if add_hf is None else int(add_hf), None)
+    return int(lib().plk_poly_lincomb_len(C.byref(job)))
+
+
+def poly_lincomb(job):
+    """plk_poly_lincomb on host bytes: job = (terms, add_hf) with terms a list of lc_term(bytes, ...);
+    returns (the L untrimmed result bytes, the trimmed length)"""
+    terms, add_hf = job
+    keep = []
+    L = max(int(np.size(_u8(t["p"])) if t.get("len") is None else t["len"]) + int(t.get("shift", 0)) for t in terms)
+    out = np.zeros(max(L, 1), np.uint8)
+    j = _lc_job(terms, add_hf, out.ctypes.data, keep, True)
+    n = _sz(0)
+    _check("plk_poly_lincomb", lib().plk_poly_lincomb(C.byref(j), C.byref(n)))
+    return bytes(out[:L]), int(n.value)
+
+
+def poly_lincomb_batch_dev(jobs, nz=None, stream=None):
+    """plk_poly_lincomb_batch_dev: jobs = [(terms, add_hf, out), ...] with device tensors / raw pointers
+    in the lc_term dicts and as out; nz: len(jobs) device uint32 words or None"""
+    keep = []
+    arr = (LcJob * max(len(jobs), 1))()
+    for i, (terms, add_hf, out) in enumerate(jobs):
+        arr[i] = _lc_job(terms, add_hf, _ptr(out), keep, False)
+    _check("plk_poly_lincomb_batch_dev", lib().plk_poly_lincomb_batch_dev(arr, len(jobs), _ptr(nz), _stream(stream)))
 
 
 # ---------------------------------------------------------------- device prover
