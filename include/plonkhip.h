@@ -191,7 +191,10 @@ int plk_dlog_generator(uint8_t out[3]);
 
 /* poly_mul on device buffers: d_out holds la+lb-1 bytes (not overlapping d_a / d_b); *d_out_nz
  * receives the trimmed length (0 = the zero polynomial, i.e. length 1).  d_work:
- * plk_poly_mul_workspace() bytes. */
+ * plk_poly_mul_workspace() bytes.  d_a, d_b and d_out may have any alignment; exactly la and lb
+ * bytes are read, exactly la+lb-1 bytes of d_out, the one word at d_out_nz and at most
+ * plk_poly_mul_workspace() bytes of d_work are written, whatever lies beside them (no kernel
+ * choice of poly_mul depends on an address). */
 size_t plk_poly_mul_workspace(size_t la, size_t lb);
 int plk_poly_mul_dev(const uint8_t *d_a, size_t la, const uint8_t *d_b, size_t lb, uint8_t *d_out,
                      uint32_t *d_out_nz, void *d_work, void *stream);
@@ -207,7 +210,9 @@ int plk_poly_mul_dev(const uint8_t *d_a, size_t la, const uint8_t *d_b, size_t l
  * input bytes for the top coefficients of wrapped products).  d_work: at least the largest single
  * job's plk_poly_mul_workspace() (a sum group of g products: g times its member's); products run
  * in launches of up to 12, cut between sum groups; plk_poly_mul_batch_workspace() bytes run every
- * size group at full width. */
+ * size group at full width.  Every a, b and out may have any alignment; exactly la and lb bytes of
+ * each operand are read, exactly la + lb - 1 bytes of each non-member out and at most work_bytes of
+ * d_work are written. */
 typedef struct {
   const uint8_t *a;
   size_t la;
@@ -539,7 +544,13 @@ int plk_prover_prove(plk_prover_t *p, const plk_circuit_t *circuit, const uint8_
                      const uint8_t rand9[9], uint8_t proof[34]);
 /* rounds 1-5 of plonk_prove from device-resident interpolated polynomials (each zero padded
  * to n bytes): f_a f_b f_c q_o q_m q_l q_r q_c s_sigma_1 s_sigma_2 s_sigma_3 acc_x l_1_x.
- * Without PLK_PROVE_STRICT non-zero remainders are tolerated (synthetic inputs). */
+ * Without PLK_PROVE_STRICT non-zero remainders are tolerated (synthetic inputs).
+ * The 13 pointers may have any alignment, each on its own; exactly n bytes of each are read and
+ * none is written, whatever lies beside them.  16-byte aligned inputs take the fused kernels (the
+ * one-launch rounds 1-3 preparation; with n % 16 == 0 also round 5's numerators inside the
+ * division launch and the chunk aggregates); q_c 4-byte aligned with n % 4 == 0 keeps t(x)'s
+ * numerator fused with its division.  Any other placement runs the byte-wise forms: more
+ * launches, the same 34 bytes. */
 int plk_prover_rounds_dev(plk_prover_t *p, const uint8_t *const d_polys[13], const uint8_t chal[5],
                           const uint8_t rand9[9], int flags, uint8_t proof[34]);
 /* Many whole proofs in one call (throughput proving of small circuits: many witnesses of one
@@ -591,7 +602,8 @@ int plk_prover_rounds_batch_dev(plk_prover_t *p, const uint8_t *d_polys, const u
  * zero padded to n) are computed once here.  plk_prover_rounds_dev with PLK_PROVE_PREPROCESSED
  * then uses them for the entries whose address equals the one given here; the bytes at those
  * addresses must not change while they are in use (call again after a change; d_polys = NULL
- * drops them).  Proof bytes are identical with and without. */
+ * drops them).  Proof bytes are identical with and without.  The six pointers may have any
+ * alignment; exactly n bytes of each are read here, and nothing of the caller's is written. */
 #define PLK_PROVE_PREPROCESSED 2
 int plk_prover_preprocess(plk_prover_t *p, const uint8_t *const d_polys[13]);
 /* Measurement of one proof (bench.py's C5 roofline; no reference counterpart).

@@ -225,6 +225,19 @@ void ref_prove4_inproc(const uint8_t *gates, const uint8_t *copies, const uint8_
   prove4_body(gates, copies, wires, chal, rnd, secret, srs_n, srs_mode, out);
 }
 
+#ifndef PLK_NO_FORK
+/* The reference leaves through exit() where it rejects.  In a forked child that would run the exit
+ * handlers and static destructors of everything the host process has loaded -- a GPU runtime among
+ * them, whose teardown in a child that does not own the device can fault, turning the reference's
+ * exit(EXIT_FAILURE) into a signal.  Registered in the child right after fork(), this handler runs
+ * before all inherited ones and ends the child with the reference's own status (the child's stdout
+ * and stderr are unbuffered or unused: nothing is left to flush). */
+static void child_leave(int status, void *arg) {
+  (void)arg;
+  _exit(status);
+}
+#endif
+
 int ref_prove4(const uint8_t *gates, const uint8_t *copies, const uint8_t *wires,
                const uint8_t *chal, const uint8_t *rnd, uint8_t secret, size_t srs_n,
                int srs_mode, uint8_t *out) {
@@ -239,6 +252,7 @@ int ref_prove4(const uint8_t *gates, const uint8_t *copies, const uint8_t *wires
   pid_t pid = fork();
   if (pid < 0) return -1;
   if (pid == 0) {
+    on_exit(child_leave, NULL);
     close(fds[0]);
     uint8_t buf[34];
     prove4_body(gates, copies, wires, chal, rnd, secret, srs_n, srs_mode, buf);
@@ -355,6 +369,7 @@ int ref_prove_n(size_t n, const uint8_t *gates, const uint8_t *copies, const uin
   pid_t pid = fork();
   if (pid < 0) { close(pfd[0]); close(pfd[1]); close(tfd[0]); close(tfd[1]); return -1; }
   if (pid == 0) {
+    on_exit(child_leave, NULL);   /* (the reference's exit() must not run the host process's handlers) */
     close(pfd[0]);
     close(tfd[0]);
     dup2(tfd[1], 1);

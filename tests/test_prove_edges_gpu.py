@@ -25,6 +25,7 @@ import torch
 import gen
 from conftest import load_golden
 from prove_ref import Prover as RefProver, ProveError
+from prove_strict_case import strict_case as _strict_case
 
 pytestmark = pytest.mark.gpu
 
@@ -327,47 +328,7 @@ def test_srs_boundary_irregular_srs(hip, oracle, n, seed):
 
 
 # ------------------------------------------------------------------ strict acceptance
-class _Recording(RefProver):
-    """remembers the remainder of its first division (t(x)'s) and the longest committed length"""
-    rem = None
-    longest = 0
-
-    def divide(self, num, den):
-        q, r = super().divide(num, den)
-        if self.rem is None:
-            self.rem = r
-        return q, r
-
-    def commit(self, p):
-        self.longest = max(self.longest, len(p))
-        return super().commit(p)
-
-
-_STRICT = {}
 STRICT_SIZES = [(37, 2), (1000, 4), (5000, 7), (65536, 41)]
-
-
-def _strict_case(oracle, n, seed):
-    """a strictly valid synthetic instance: q_c = -(the t(x) remainder at q_c = 0), Z_H = x^n - 1
-    having one more coefficient than q_c (once per module: 2^16 costs seconds of oracle time)"""
-    if n not in _STRICT:
-        polys, chal, rnd, zh, pts = gen.prove_instance(n, seed, 2 * n + 8)
-        polys = [p.copy() for p in polys]
-        dense = polys[QC].copy()
-        polys[QC] = np.zeros(n, np.uint8)
-        rec = _ref(oracle, pts, n, zh, _Recording)
-        loose = rec.rounds(polys, chal, rnd, strict=False)
-        r = np.zeros(n, np.int64)
-        r[:len(rec.rem)] = rec.rem
-        assert np.any(r) and len(rec.rem) <= n
-        polys[QC] = ((17 - r) % 17).astype(np.uint8)
-        ref = _ref(oracle, pts, n, zh, _Recording)
-        want = ref.rounds(polys, chal, rnd, strict=True)
-        # q_c only moves the remainder: the same bytes with q_c = 0 and with the instance's dense q_c
-        assert want == loose
-        _STRICT[n] = dict(n=n, polys=polys, chal=chal, rnd=rnd, zh=zh, pts=pts, want=want, lstar=ref.longest,
-                          dense_qc=dense)
-    return _STRICT[n]
 
 
 @pytest.mark.parametrize("n,seed", STRICT_SIZES)
