@@ -344,6 +344,55 @@ int plk_poly_lincomb(const plk_lc_job_t *job, size_t *out_len);  /* host buffers
 int plk_poly_lincomb_batch_dev(const plk_lc_job_t *jobs, int n, uint32_t *d_nz /* n words or NULL */,
                                void *stream);
 
+/* ---- division by short divisors: a ragged batch, one streaming scan each -----------------
+ * poly_divide (src/poly.h:124-177) of device polynomials by divisors of 2 .. PLK_DIV_SHORT_MAX coefficients
+ * (degree t = dl - 1 in 1 .. 16: x - z, (x - z)(x - z omega), a vanishing polynomial Z_S of a small point
+ * set, the dense Z_H of n <= 16), a whole batch per call.  Division by such a divisor is a t-state linear
+ * recurrence over the numerator from its top coefficient down; it runs as one scan whose traffic is two
+ * reads and one write of the numerator.  plk_poly_divide(_dev) and their routing are
+ * unchanged and do not use this path.
+ *
+ * Semantics (the specification).  For every numerator whose bytes are all < 17, job b's quot bytes, rem
+ * bytes and trimmed lengths equal those of plk_poly_divide(num, nl, den, dl, ...), nl < dl included (q =
+ * {0}, rem = num).  The outputs are untrimmed: max(nl - dl + 1, 1) quotient bytes and min(dl - 1, nl)
+ * remainder bytes, every one written.  d_lens[3b] and d_lens[3b + 1] receive the index + 1 of the last
+ * non-zero quotient and remainder byte (0: all zero), d_lens[3b + 2] is 0, or 1 when the numerator holds a
+ * byte >= 17.  _dev form: a job with status 1 has unspecified bytes inside its own quot and rem buffers and
+ * unspecified length words; its neighbours are unaffected.  Host form: such a job runs through
+ * plk_poly_divide, so the call is exact for every numerator byte (the convention of plk_kzg_open_batch);
+ * quot_lens / rem_lens are trimmed as plk_poly_divide returns them (>= 1).
+ * d_work: plk_poly_divide_short_workspace(jobs, n) bytes; neither it nor d_lens needs initialisation, and
+ * a workspace may be reused by the next call on the same stream.  den is a HOST array and is not referenced
+ * after the call returns.  Any n: the jobs run grouped by divisor length class (dl <= 3, <= 5, <= 9, <= 17),
+ * PLK_DIV_SHORT_LAUNCH_JOBS jobs to a group; a group is one kernel when every job of it fits one block's
+ * span and three otherwise, one memset node in front of the call's launches.  Pointers may have any
+ * alignment (d_lens: 4 bytes).  An output may overlap no input and no other output of the call.  Calls on
+ * different streams with distinct workspaces may run concurrently.
+ * Errors (all raised before any device query): a NULL pointer, n <= 0, nl == 0, dl < 2, a divisor byte >= 17
+ * or a zero lead are PLK_ERR_ARG; dl > PLK_DIV_SHORT_MAX or nl >= 2^32 is PLK_ERR_RANGE.  No GPU is
+ * PLK_ERR_NODEV.  The device rules are those of plk_kzg_verify_batch(_dev).
+ * plk_poly_divide_short_plan (host only) fills out[] for one job of shape (nl, dl) run alone: {kernels (1 or
+ * 3), coefficients per thread, coefficients per block, the largest nl of this dl that runs as one kernel};
+ * it returns PLK_ERR_ARG / PLK_ERR_RANGE as the launch would.
+ * plk_poly_from_roots (host only) writes the t + 1 coefficients of prod (x - roots[i]), t in 1 .. 16, roots
+ * < 17, repeats allowed (PLK_ERR_ARG: NULL, t < 1, a root >= 17; PLK_ERR_RANGE: t > 16): the Z_S of a
+ * point set. */
+#define PLK_DIV_SHORT_MAX 17          /* divisor coefficients: degree 1..16 */
+#define PLK_DIV_SHORT_LAUNCH_JOBS 32  /* jobs a group of launches carries */
+typedef struct {
+  const uint8_t *num; size_t nl;  /* device pointer in the _dev form; nl >= 1 */
+  const uint8_t *den; size_t dl;  /* HOST array, 2..PLK_DIV_SHORT_MAX bytes, all < 17, den[dl-1] != 0 */
+  uint8_t *quot;                  /* max(nl - dl + 1, 1) bytes, every one written */
+  uint8_t *rem;                   /* min(dl - 1, nl) bytes, every one written */
+} plk_divshort_job_t;
+size_t plk_poly_divide_short_workspace(const plk_divshort_job_t *jobs, int n); /* host only; 0: bad args */
+int plk_poly_divide_short_plan(size_t nl, size_t dl, int out[4]);              /* host only */
+int plk_poly_divide_short_batch_dev(const plk_divshort_job_t *jobs, int n,
+                                    uint32_t *d_lens /* 3 n words */, void *d_work, void *stream);
+int plk_poly_divide_short_batch(const plk_divshort_job_t *jobs, int n,
+                                size_t *quot_lens, size_t *rem_lens);          /* host buffers, synchronous */
+int plk_poly_from_roots(const uint8_t *roots, int t, uint8_t *out /* t + 1 */); /* host only */
+
 /* ---- KZG over a resident SRS: commit and open, batched ----------------------------------
  * The commitment (srs_eval_at_s, src/srs.h:53-68) and the opening the reference spells out twice per
  * proof (src/plonk.h:606-621: y = p(z), q = (p - y) / (x - z), [q]) against an SRS that stays on the

@@ -117,6 +117,11 @@ SIGNATURES = {
     "plk_poly_lincomb_len": (_sz, [_vp]),
     "plk_poly_lincomb": (C.c_int, [_vp, C.POINTER(_sz)]),
     "plk_poly_lincomb_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "plk_poly_divide_short_workspace": (_sz, [_vp, C.c_int]),
+    "plk_poly_divide_short_plan": (C.c_int, [_sz, _sz, C.POINTER(C.c_int)]),
+    "plk_poly_divide_short_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "plk_poly_divide_short_batch": (C.c_int, [_vp, C.c_int, C.POINTER(_sz), C.POINTER(_sz)]),
+    "plk_poly_from_roots": (C.c_int, [_u8p, C.c_int, _u8p]),
 }
 
 # PLK_OPT_* (include/plonkhip.h), by the name without the prefix
@@ -806,6 +811,74 @@ def poly_lincomb_batch_dev(jobs, nz=None, stream=None):
     for i, (terms, add_hf, out) in enumerate(jobs):
         arr[i] = _lc_job(terms, add_hf, _ptr(out), keep, False)
     _check("plk_poly_lincomb_batch_dev", lib().plk_poly_lincomb_batch_dev(arr, len(jobs), _ptr(nz), _stream(stream)))
+
+
+# ---------------------------------------------------------------- division by short divisors
+PLK_DIV_SHORT_MAX = 17
+PLK_DIV_SHORT_LAUNCH_JOBS = 32
+
+
+class DivShortJob(C.Structure):
+    """plk_divshort_job_t"""
+    _fields_ = [("num", C.c_void_p), ("nl", _sz), ("den", C.c_void_p), ("dl", _sz), ("quot", C.c_void_p),
+                ("rem", C.c_void_p)]
+
+
+def _divshort_jobs(jobs, keep):
+    """jobs: (num, nl, den, quot, rem) with num / quot / rem device tensors or raw pointers, den HOST bytes"""
+    arr = (DivShortJob * max(len(jobs), 1))()
+    for i, (num, nl, den, quot, rem) in enumerate(jobs):
+        d = _u8(den).reshape(-1)
+        keep.append(d)
+        arr[i] = DivShortJob(_ptr(num), int(nl), d.ctypes.data, d.size, _ptr(quot), _ptr(rem))
+    return arr
+
+
+def poly_divide_short_workspace(shapes):
+    """plk_poly_divide_short_workspace for [(nl, dl), ...]: bytes of d_work; 0 for bad arguments.  No device
+    needed."""
+    arr = (DivShortJob * max(len(shapes), 1))(*[DivShortJob(1, int(nl), 1, int(dl), 1, 1) for nl, dl in shapes])
+    return int(lib().plk_poly_divide_short_workspace(arr, len(shapes)))
+
+
+def poly_divide_short_plan(nl, dl):
+    """plk_poly_divide_short_plan: one job of shape (nl, dl) run alone.  No device needed."""
+    out = (C.c_int * 4)()
+    _check("plk_poly_divide_short_plan", lib().plk_poly_divide_short_plan(int(nl), int(dl), out))
+    return dict(zip(("kernels", "per_thread", "per_block", "one_kernel_max"), list(out)))
+
+
+def poly_divide_short_batch(nums, dens):
+    """plk_poly_divide_short_batch on host bytes: [(quot, rem)] trimmed as poly_divide returns them"""
+    keep, n = [], len(nums)
+    arr = (DivShortJob * max(n, 1))()
+    outs = []
+    for i, (num, den) in enumerate(zip(nums, dens)):
+        a, d = _u8(num).reshape(-1), _u8(den).reshape(-1)
+        q, r = np.zeros(max(a.size, 1), np.uint8), np.zeros(max(a.size, 1), np.uint8)
+        keep += [a, d]
+        outs.append((q, r))
+        arr[i] = DivShortJob(a.ctypes.data, a.size, d.ctypes.data, d.size, q.ctypes.data, r.ctypes.data)
+    ql, rl = (_sz * max(n, 1))(), (_sz * max(n, 1))()
+    _check("plk_poly_divide_short_batch", lib().plk_poly_divide_short_batch(arr, n, ql, rl))
+    return [(bytes(q[:ql[i]]), bytes(r[:rl[i]])) for i, (q, r) in enumerate(outs)]
+
+
+def poly_divide_short_batch_dev(jobs, lens, work, stream=None):
+    """plk_poly_divide_short_batch_dev: jobs = [(num, nl, den, quot, rem), ...] (device tensors / raw
+    pointers, den HOST bytes); lens: 3 len(jobs) device uint32 words; work: poly_divide_short_workspace bytes"""
+    keep = []
+    arr = _divshort_jobs(jobs, keep)
+    _check("plk_poly_divide_short_batch_dev",
+           lib().plk_poly_divide_short_batch_dev(arr, len(jobs), _ptr(lens), _ptr(work), _stream(stream)))
+
+
+def poly_from_roots(roots):
+    """plk_poly_from_roots: the coefficients of prod (x - r), low degree first.  No device needed."""
+    r = _u8(roots).reshape(-1)
+    out = np.zeros(r.size + 1, np.uint8)
+    _check("plk_poly_from_roots", lib().plk_poly_from_roots(_p(r), r.size, _p(out)))
+    return bytes(out)
 
 
 # ---------------------------------------------------------------- device prover
