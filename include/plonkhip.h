@@ -393,6 +393,52 @@ int plk_poly_divide_short_batch(const plk_divshort_job_t *jobs, int n,
                                 size_t *quot_lens, size_t *rem_lens);          /* host buffers, synchronous */
 int plk_poly_from_roots(const uint8_t *roots, int t, uint8_t *out /* t + 1 */); /* host only */
 
+/* ---- products by short operands: whole runs of equal-shape products in one launch -------
+ * poly_mul (src/poly.h:106-122) of device polynomials where the shorter operand has at most
+ * PLK_MUL_SHORT_MAX coefficients: the many small products of small circuits, and long polynomials times a
+ * blinding polynomial, a Z_S from plk_poly_from_roots or a selector of a few hundred coefficients.  The
+ * products run as a schoolbook convolution over packed bytes, any number of them per
+ * launch.  plk_poly_mul, plk_poly_mul_dev, plk_poly_mul_batch_dev and their routing are unchanged and do not
+ * use this path.
+ *
+ * A run is count products of one shape at fixed strides: product i reads la bytes at a + i * a_stride and lb
+ * bytes at b + i * b_stride and writes la + lb - 1 bytes at out + i * out_stride.  A ragged batch is a list of
+ * runs with count = 1.  Any stride may be 0 (a shared operand) or smaller than the operand (overlapping
+ * reads).  The run array is a HOST array and is not referenced after the call returns.
+ *
+ * Semantics (the specification).  Product i of run r writes exactly the la + lb - 1 untrimmed bytes that
+ * plk_poly_mul(a_i, la, b_i, lb, ...) produces, for EVERY input byte value: hf_mul reduces each product and
+ * hf_add keeps the sum canonical (src/hf.h:79-109), so the result is conv(a mod 17, b mod 17) mod 17.  Bytes
+ * between consecutive outputs (out_stride > la + lb - 1) are not written.  d_nz may be NULL; otherwise it
+ * holds one word per product in run order (product i of run r at count_0 + ... + count_{r-1} + i), each
+ * receiving the index + 1 of the last non-zero output byte (0: all zero) -- the convention of
+ * plk_poly_mul_dev -- and needs no initialisation by the caller (one memset node in front of the launches).
+ * Host form: synchronous, staged through device buffers on the primary device; out_lens (one entry per
+ * product, may be NULL) is trimmed as plk_poly_mul returns it (>= 1).
+ * Batch: any n; a launch carries PLK_MUL_SHORT_LAUNCH_RUNS whole runs, larger batches run as consecutive
+ * launches on the stream.  No workspace, no state; pointers may have any alignment (d_nz: 4 bytes).  An
+ * output may overlap no input and no other output of the call.  Calls on different streams may run
+ * concurrently.
+ * Errors (all raised before any device query): a NULL runs, a, b or out, n <= 0, count == 0, la == 0,
+ * lb == 0, or count > 1 with out_stride < la + lb - 1 are PLK_ERR_ARG; min(la, lb) > PLK_MUL_SHORT_MAX,
+ * la + lb - 1 >= 2^32, more than 2^24 products in one call, or a run that alone needs more blocks than a
+ * grid holds are PLK_ERR_RANGE.  No GPU is PLK_ERR_NODEV -- there is no CPU fallback.  The device rules are
+ * those of plk_kzg_verify_batch(_dev).
+ * plk_poly_mul_short_plan (host only) fills out[] for one run of count products of shape (la, lb) alone:
+ * {outputs per work unit, work units per product, work units per block, blocks}; it returns the error the
+ * launch would return. */
+#define PLK_MUL_SHORT_MAX 1024          /* coefficients of the shorter operand */
+#define PLK_MUL_SHORT_LAUNCH_RUNS 32    /* whole runs a launch carries */
+typedef struct {
+  const uint8_t *a; size_t la; size_t a_stride;   /* product i reads la bytes at a + i * a_stride   */
+  const uint8_t *b; size_t lb; size_t b_stride;   /* ... and lb bytes at b + i * b_stride           */
+  uint8_t *out;     size_t out_stride;            /* writes la + lb - 1 bytes at out + i * out_stride */
+  size_t count;                                   /* >= 1 products of this one shape                 */
+} plk_mulshort_run_t;                             /* pointers: device in the _dev form, host in the host form */
+int plk_poly_mul_short_plan(size_t la, size_t lb, size_t count, int64_t out[4]);           /* host only */
+int plk_poly_mul_short_batch_dev(const plk_mulshort_run_t *runs, int n, uint32_t *d_nz, void *stream);
+int plk_poly_mul_short_batch(const plk_mulshort_run_t *runs, int n, size_t *out_lens);
+
 /* ---- KZG over a resident SRS: commit and open, batched ----------------------------------
  * The commitment (srs_eval_at_s, src/srs.h:53-68) and the opening the reference spells out twice per
  * proof (src/plonk.h:606-621: y = p(z), q = (p - y) / (x - z), [q]) against an SRS that stays on the

@@ -122,6 +122,9 @@ SIGNATURES = {
     "plk_poly_divide_short_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "plk_poly_divide_short_batch": (C.c_int, [_vp, C.c_int, C.POINTER(_sz), C.POINTER(_sz)]),
     "plk_poly_from_roots": (C.c_int, [_u8p, C.c_int, _u8p]),
+    "plk_poly_mul_short_plan": (C.c_int, [_sz, _sz, _sz, C.POINTER(C.c_int64)]),
+    "plk_poly_mul_short_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "plk_poly_mul_short_batch": (C.c_int, [_vp, C.c_int, C.POINTER(_sz)]),
 }
 
 # PLK_OPT_* (include/plonkhip.h), by the name without the prefix
@@ -879,6 +882,78 @@ def poly_from_roots(roots):
     out = np.zeros(r.size + 1, np.uint8)
     _check("plk_poly_from_roots", lib().plk_poly_from_roots(_p(r), r.size, _p(out)))
     return bytes(out)
+
+
+# ---------------------------------------------------------------- products by short operands
+PLK_MUL_SHORT_MAX = 1024
+PLK_MUL_SHORT_LAUNCH_RUNS = 32
+
+
+class MulShortRun(C.Structure):
+    """plk_mulshort_run_t"""
+    _fields_ = [("a", C.c_void_p), ("la", _sz), ("a_stride", _sz), ("b", C.c_void_p), ("lb", _sz), ("b_stride", _sz),
+                ("out", C.c_void_p), ("out_stride", _sz), ("count", _sz)]
+
+
+def mul_short_run(a, la, b, lb, out, count=1, a_stride=0, b_stride=0, out_stride=0):
+    """a MulShortRun from device tensors / raw pointers: count products of la x lb coefficients, product i at
+    a + i a_stride, b + i b_stride, out + i out_stride"""
+    return MulShortRun(_ptr(a), int(la), int(a_stride), _ptr(b), int(lb), int(b_stride), _ptr(out), int(out_stride),
+                       int(count))
+
+
+def poly_mul_short_plan(la, lb, count=1):
+    """plk_poly_mul_short_plan: one run of count products of shape (la, lb) alone.  No device needed."""
+    out = (C.c_int64 * 4)()
+    _check("plk_poly_mul_short_plan", lib().plk_poly_mul_short_plan(int(la), int(lb), int(count), out))
+    return dict(zip(("per_unit", "units_per_product", "units_per_block", "blocks"), [int(v) for v in out]))
+
+
+def poly_mul_short_batch(runs):
+    """plk_poly_mul_short_batch on host bytes.  A run is (a, b) -- one product -- or (a, la, a_stride, b, lb,
+    b_stride, count) over host arrays that hold every operand of the run.  Returns the products in run order,
+    trimmed as poly_mul returns them."""
+    keep, outs = [], []
+    arr = (MulShortRun * max(len(runs), 1))()
+    for i, run in enumerate(runs):
+        if len(run) == 2:
+            a, b = _u8(run[0]).reshape(-1), _u8(run[1]).reshape(-1)
+            la, sa, lb, sb, count = a.size, 0, b.size, 0, 1
+        else:
+            a, la, sa, b, lb, sb, count = run
+            a, b = _u8(a).reshape(-1), _u8(b).reshape(-1)
+            if count < 1 or la < 1 or lb < 1 or (count - 1) * sa + la > a.size or (count - 1) * sb + lb > b.size:
+                raise ValueError("run %d: the arrays do not hold count operands at these strides" % i)
+        lo = max(int(la) + int(lb) - 1, 1)
+        out = np.zeros(max(int(count), 1) * lo, np.uint8)
+        keep += [a, b]
+        outs.append((out, lo, int(count)))
+        arr[i] = MulShortRun(a.ctypes.data, int(la), int(sa), b.ctypes.data, int(lb), int(sb), out.ctypes.data, lo,
+                             int(count))
+    total = sum(c for _, _, c in outs)
+    lens = (_sz * max(total, 1))()
+    _check("plk_poly_mul_short_batch", lib().plk_poly_mul_short_batch(arr, len(runs), lens))
+    res, k = [], 0
+    for out, lo, count in outs:
+        for i in range(count):
+            res.append(bytes(out[i * lo:i * lo + lens[k]]))
+            k += 1
+    return res
+
+
+def poly_mul_short_batch_dev(runs, nz=None, stream=None):
+    """plk_poly_mul_short_batch_dev: runs = MulShortRun structures (mul_short_run) or (a, la, a_stride, b, lb,
+    b_stride, out, out_stride, count) tuples over device tensors / raw pointers; nz: one device uint32 word per
+    product in run order, or None"""
+    arr = (MulShortRun * max(len(runs), 1))()
+    for i, r in enumerate(runs):
+        if isinstance(r, MulShortRun):
+            arr[i] = r
+        else:
+            a, la, sa, b, lb, sb, out, so, count = r
+            arr[i] = MulShortRun(_ptr(a), int(la), int(sa), _ptr(b), int(lb), int(sb), _ptr(out), int(so), int(count))
+    _check("plk_poly_mul_short_batch_dev",
+           lib().plk_poly_mul_short_batch_dev(arr, len(runs), _ptr(nz), _stream(stream)))
 
 
 # ---------------------------------------------------------------- device prover
