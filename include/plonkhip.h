@@ -89,21 +89,16 @@ enum {
                                     it runs on 2^13 tiles -- one launch fewer -- else as 1) */
   PLK_OPT_NTT_TABLE_SHARE = 19,  /* 1: a table pass runs several arrays of one tile per block (column words read once) */
   PLK_OPT_NTT_LAUNCH_LOG = 20,   /* diagnostics: 1 records the NTT passes' launch plans (plk_ntt_launch_log) */
-  PLK_OPT_PROVE_FUSE_DIV = 21,   /* 1: round 5's numerators and their divisions by x - z, x - z omega in one
-                                    launch (single-pass suffix scan); 0: numerators, then the apply launch */
   PLK_OPT_PROVE_SRS_LOGS = 22,   /* 1: the prover's commitments read its SRS in log form (1 B per point,
                                     converted once at plk_prover_create); 0: the G1 form (3 B) */
   PLK_OPT_PROVE_PACK_FUSE = 23,  /* 1 (with PROVE_SRS_LOGS): commitments, trimmed lengths and the proof packing
                                     in one launch (commit_pack_kernel); 0: the MSM, then trim_pack_kernel */
   PLK_OPT_PROVE_EARLY_COMMITS = 24, /* 1 (with PROVE_PACK_FUSE): the 7 commitments that do not wait for round 5
-                                       run as extra rows of round 5's scan launch; 2: of round 4's evaluation
-                                       launch */
+                                       run as extra rows of round 5's fused division launch; 0: with the
+                                       other two in commit_pack_kernel */
   PLK_OPT_PROVE_HELPER_COPY = 25, /* 1: helpers of plk_prover_attach_helpers on the proving device itself take
                                      the distinct-device input path (their inputs copied into their own rows,
                                      the rest pointed at a poison row): a one-GPU test of that branch */
-  PLK_OPT_PROVE_EVAL_AGG = 26,   /* 1: round 4's evaluation rows also store round 5's scan-chunk aggregates, so
-                                    both round-5 divisions finish in ONE launch (lincomb_agg_divide_kernel);
-                                    0: the numerators + aggregates launch, then the apply launch */
   PLK_OPT_DROPIN_HOST_WORK = 28, /* drop-in headers (include/plk_host.h): a call whose host cost estimate (about
                                     ns: la*lb MACs for poly_mul, 300 per MSM point, ...) is at most this stays
                                     on the host; 32768 ~ one GPU round trip; 0: every call on the GPU.  The
@@ -113,7 +108,8 @@ enum {
                                     quotient comes from a Newton inverse over the exact poly_mul products
                                     instead of the reference's loop on one GPU thread.  0: never, 1: whenever
                                     eligible; default 256, the measured crossover */
-  /* retired (no enumerator; set: PLK_ERR_ARG, get: -1): 27 PROVE_GRAPH */
+  /* 21, 26, 27: retired (no enumerator; set: PLK_ERR_ARG, get: -1): PROVE_FUSE_DIV, PROVE_EVAL_AGG,
+     PROVE_GRAPH */
   PLK_OPT_COUNT = 30
 };
 int plk_set_option(int opt, int64_t value);   /* PLK_ERR_ARG: unknown option or value out of range */

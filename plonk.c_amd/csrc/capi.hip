@@ -477,12 +477,12 @@ const OptDef kOpt[PLK_OPT_COUNT] = {
     {2, 0, 2, false},                          // PROVE_DERIVE_T2A (2: in the t_2 product's first pass)
     {1, 0, 1, false},                          // NTT_TABLE_SHARE
     {0, 0, 1, false},                          // NTT_LAUNCH_LOG
-    {0, 0, 1, false},                          // PROVE_FUSE_DIV (measured slower)
+    kRetired,                                  // 21
     {1, 0, 1, false},                          // PROVE_SRS_LOGS
     {1, 0, 1, false},                          // PROVE_PACK_FUSE
-    {1, 0, 2, false},                          // PROVE_EARLY_COMMITS (2: in round 4's evaluation launch)
+    {1, 0, 1, false},                          // PROVE_EARLY_COMMITS
     {0, 0, 1, false},                          // PROVE_HELPER_COPY (tests: the distinct-device input path on one GPU)
-    {1, 0, 1, false},                          // PROVE_EVAL_AGG
+    kRetired,                                  // 26
     kRetired,                                  // 27
     {32768, 0, 1ll << 40, false},              // DROPIN_HOST_WORK (read by include/plk_host.h only)
     {256, 0, 1ll << 62, false},                // DIVIDE_FAST_MIN (measured crossover)

@@ -442,7 +442,7 @@ struct EvArgs {
   // the row's partial enters its evaluation times x^mexp (a slice of a longer polynomial whose offset
   // is not 0 mod 16: t(x) from t_lo / t_mid / t_hi)
   int mexp[EV_ROWS];
-  // chunk aggregates for round 5's divisions (PLK_OPT_PROVE_EVAL_AGG): col >= 0 stores, for every
+  // chunk aggregates for round 5's divisions (lincomb_agg_divide_kernel): col >= 0 stores, for every
   // 4096-coefficient chunk c of the row's polynomial, sum_{i in c} p[i] x^i mod 17 at
   // agg[16 (coff + c) + col] (coff: the row's first chunk, a split row's offset / 4096)
   int col[EV_ROWS];
@@ -558,8 +558,13 @@ __device__ __forceinline__ void eval_row_block(const EvArgs& a, int e, uint32_t 
 // an evaluation adds the finished value with a ticket to the top word; the last of those writes
 // every S[out] and runs the round's scalar program -- the partial / final / scalar kernels of a
 // three-launch chain in one.
-// (optional) commitments that do not wait for round 5, run as extra grid rows of an earlier launch
-// (round 5's scan, or round 4's evaluations): rows y >= nd are log-form MSMs of arena rows
+__global__ __launch_bounds__(256) void eval_kernel(EvArgs a, uint8_t* __restrict__ S, uint32_t* __restrict__ tick,
+                                                   uint32_t* __restrict__ stat) {
+  eval_row_block(a, (int)blockIdx.y, blockIdx.x, gridDim.x, S, tick, stat, true);
+}
+
+// (optional) commitments that do not wait for round 5, run as extra grid rows of round 5's
+// division launch (lincomb_agg_divide_kernel): rows y >= nd are log-form MSMs of arena rows
 // 0 .. nrows - 1 on X blocks each
 // points per commitment row: each row's own upper-bound length (the arena row is zero past it),
 // not the arena's stride -- w_z(x)'s quotient is ~2n long, the other eight ~n
@@ -576,19 +581,6 @@ struct EarlyMsm {
   int nrows, nd;
   uint32_t X;
 };
-__global__ __launch_bounds__(256) void eval_kernel(EvArgs a, uint8_t* __restrict__ S, uint32_t* __restrict__ tick,
-                                                   uint32_t* __restrict__ stat, EarlyMsm em) {
-  if ((int)blockIdx.y >= a.nr) {   // (uniform) an early commitment row
-    __shared__ uint32_t etab[PLK_GROUP_ORDER];
-    __shared__ uint32_t wsum[256 / PLK_WAVE];
-    __shared__ uint32_t wbad[256 / PLK_WAVE];
-    const int r = (int)blockIdx.y - a.nr;
-    (void)msm_log_block<256>(em.logs, em.arena + (uint64_t)r * em.cstride, em.rl.n[r], blockIdx.x, gridDim.x, (uint32_t)r,
-                             em.res + r, em.exp_words, etab, wsum, wbad);
-    return;
-  }
-  eval_row_block(a, (int)blockIdx.y, blockIdx.x, gridDim.x, S, tick, stat, true);
-}
 
 // ------------------------------------------------------------------ poly_divide
 // (a) divisor L x^m + c (Z_H of a multiplicative subgroup is x^n - 1): the long division
@@ -930,11 +922,6 @@ __device__ __forceinline__ void lc_swar(const LcArgs& a, const uint32_t (&cf)[LC
     acc[4 * q + 3] = O[q] >> 16;
   }
 }
-__device__ __forceinline__ void lc16_swar(const LcArgs& a, const uint32_t (&cf)[LC_MAX], uint32_t c0, uint32_t c1,
-                                          uint64_t i, uint32_t (&acc)[16]) {
-  lc_swar<4>(a, cf, c0, c1, i, acc);
-}
-
 __global__ __launch_bounds__(SCAN_T) void lin_scan_sums_kernel(LinDivs L, const uint8_t* __restrict__ S) {
   const LinDiv& D = L.d[blockIdx.y];
   if ((int)blockIdx.x >= D.nb) return;
@@ -953,58 +940,6 @@ __global__ __launch_bounds__(SCAN_T) void lin_scan_sums_kernel(LinDivs L, const 
     if (i < nl && i > 0) acc += num[i] * pw[i & 15];
   }
   const uint32_t t = scan_block_sum(acc % HFP);
-  if (threadIdx.x == 0) D.bsum[blockIdx.x] = t % HFP;
-}
-
-// Round 5's two numerators (w_z(x)'s lincomb, z(x) - z_omega_z) and the scan's block aggregates
-// in one launch: block (c, d) writes numerator d's coefficients [4096 c, 4096 (c+1)) and their
-// aggregate sum_{i > 0} num[i] a^i.  Every term is 16-byte aligned and readable in whole 16-byte
-// chunks up to its length (host-checked), so each term's uint4 load is issued unconditionally
-// (clamped address, masked bytes) and all of them are in flight together.
-__global__ __launch_bounds__(SCAN_T) void lincomb_scan_kernel(LcBatch b, LinDivs L, const uint8_t* __restrict__ S,
-                                                             EarlyMsm em) {
-  if ((int)blockIdx.y >= em.nd) {   // (uniform) an early commitment row
-    __shared__ uint32_t etab[PLK_GROUP_ORDER];
-    __shared__ uint32_t wsum[SCAN_T / PLK_WAVE];
-    __shared__ uint32_t wbad[SCAN_T / PLK_WAVE];
-    const int r = (int)blockIdx.y - em.nd;
-    if (blockIdx.x >= em.X) return;
-    (void)msm_log_block<SCAN_T>(em.logs, em.arena + (uint64_t)r * em.cstride, em.rl.n[r], blockIdx.x, em.X, (uint32_t)r,
-                                em.res + r, em.exp_words, etab, wsum, wbad);
-    return;
-  }
-  const int d = blockIdx.y;
-  const LcArgs& a = b.a[d];
-  const LinDiv& D = L.d[d];
-  if ((int)blockIdx.x >= D.nb) return;
-  uint32_t cf[LC_MAX];
-#pragma unroll
-  for (int t = 0; t < LC_MAX; t++) cf[t] = t < a.nt ? S[a.slot[t]] : 0u;
-  const uint32_t sc = S[a.scale];
-  const uint32_t c0 = a.c0 >= 0 ? S[a.c0] : 0u, c1 = a.c1 >= 0 ? S[a.c1] : 0u;
-  const uint64_t i = (uint64_t)blockIdx.x * SCAN_B + (uint64_t)threadIdx.x * SCAN_E;
-  uint32_t acc[16];
-  lc16_swar(a, cf, c0, c1, i, acc);
-  const uint32_t av = S[D.aslot];
-  uint32_t pw[16];
-  pw[0] = 1;
-#pragma unroll
-  for (int j = 1; j < 16; j++) pw[j] = pw[j - 1] * av % HFP;
-  uint32_t o[4] = {0, 0, 0, 0}, agg = 0;
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    const uint32_t v = i + k < a.out_len ? hmod(hmod(acc[k]) * sc) : 0u;   // (acc <= 16 x 16 x 255 + 32)
-    o[k >> 2] |= v << (8 * (k & 3));
-    if (i + k > 0) agg += v * pw[k];   // (i + k) mod 16 = k
-  }
-  if (i + 16 <= a.out_len) {
-    *reinterpret_cast<uint4*>(a.out + i) = make_uint4(o[0], o[1], o[2], o[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 16; k++)
-      if (i + k < a.out_len) a.out[i + k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
-  }
-  const uint32_t t = scan_block_sum(agg % HFP);
   if (threadIdx.x == 0) D.bsum[blockIdx.x] = t % HFP;
 }
 
@@ -1077,16 +1012,20 @@ __global__ __launch_bounds__(SCAN_T) void lin_scan_apply_kernel(LinDivs L, const
 }
 
 // The quotient bytes of one 4096-coefficient chunk of a division by x - av, from the chunk's
-// numerator bytes (nb8: this thread's E, packed), the thread's powers pt[k] = av^(base + k) and
+// numerator bytes (nb8: this thread's AGG_E, packed), the thread's powers pt[k] = av^(base + k) and
 // ipt[k] = av^-(base + k + 1) (exponents mod 16), and the carry (this thread's part of the sum of
-// every later chunk's aggregate, < 17) -- lin_scan_apply_kernel's work on packed coefficients,
-// shared by the one-launch divisions.  T threads of E coefficients each: T E = 4096.
-template <int T, int E>
+// every later chunk's aggregate, < 17) -- lin_scan_apply_kernel's work on packed coefficients, for
+// lincomb_agg_divide_kernel.
+// 512 threads of 8 coefficients per 4096-coefficient chunk: twice the waves of a 16-coefficient
+// form over the same ~770 chunks (one block each), so more of each block's load -> sum -> scan chain
+// overlaps (the chain, not the bytes, bounds this launch)
+constexpr int AGG_T = 512, AGG_E = SCAN_B / AGG_T;
 __device__ __forceinline__ void lin_div_finish(const LcArgs& a, const LinDiv& D, const uint32_t (&cf)[LC_MAX],
                                                uint32_t sc, uint32_t av, uint64_t base, uint64_t nl,
-                                               const uint32_t (&nb8)[E / 4], const uint32_t (&pt)[E],
-                                               const uint32_t (&ipt)[E], uint32_t carry) {
-  static_assert(T * E == SCAN_B && E % 4 == 0, "a scan chunk");
+                                               const uint32_t (&nb8)[AGG_E / 4], const uint32_t (&pt)[AGG_E],
+                                               const uint32_t (&ipt)[AGG_E], uint32_t carry) {
+  constexpr int T = AGG_T, E = AGG_E;
+  static_assert(T * E == SCAN_B && E == 8, "a scan chunk, one uint2 of quotient bytes per thread");
   uint32_t w[E], tot = 0;
 #pragma unroll
   for (int k = 0; k < E; k++) {
@@ -1137,8 +1076,7 @@ __device__ __forceinline__ void lin_div_finish(const LcArgs& a, const LinDiv& D,
   }
   uint8_t* q = D.q;
   if (D.vec && base + E <= ql) {
-    if constexpr (E == 16) *reinterpret_cast<uint4*>(q + base) = make_uint4(o[0], o[1], o[2], o[3]);
-    else *reinterpret_cast<uint2*>(q + base) = make_uint2(o[0], o[1]);
+    *reinterpret_cast<uint2*>(q + base) = make_uint2(o[0], o[1]);
   } else {
 #pragma unroll
     for (int k = 0; k < E; k++)
@@ -1160,72 +1098,7 @@ __device__ __forceinline__ void div_powers(uint32_t av, uint32_t (&pw)[16], uint
   }
 }
 
-// Round 5 in ONE launch (PLK_OPT_PROVE_FUSE_DIV): each block forms its 4096-coefficient chunk
-// of the numerator in registers (lincomb_scan_kernel's loads), publishes the chunk's aggregate
-// as one 64-bit word {epoch, sum}, then reduces the aggregates of every later chunk and finishes
-// its quotient bytes as lin_scan_apply_kernel does -- the numerator is never stored or re-read.
-// Chunks are taken in REVERSE block order: a block waits only for chunks owned by blocks that
-// were dispatched before it (running or done), so the waits cannot deadlock whatever the
-// residency.  A wait that still sees a stale word after ~2^22 polls gives up and marks the
-// division's remainder word with SCAN_TIMEOUT (reported as an internal error, never a proof).
-constexpr uint32_t SCAN_TIMEOUT = 1u << 30;
-__global__ __launch_bounds__(SCAN_T) void lincomb_divide_kernel(LcBatch b, LinDivs L, const uint8_t* __restrict__ S,
-                                                               unsigned long long* __restrict__ fw0, uint32_t fw_stride,
-                                                               uint32_t epoch) {
-  const int d = blockIdx.y;
-  const LcArgs& a = b.a[d];
-  const LinDiv& D = L.d[d];
-  const int c = (int)(gridDim.x - 1 - blockIdx.x);   // this block's chunk
-  if (c >= D.nb) return;
-  unsigned long long* fw = fw0 + (uint64_t)d * fw_stride;
-  // (the scalars are uniform: read into SGPRs, so the power tables below cost no VGPRs)
-  uint32_t cf[LC_MAX];
-#pragma unroll
-  for (int t = 0; t < LC_MAX; t++) cf[t] = __builtin_amdgcn_readfirstlane(t < a.nt ? S[a.slot[t]] : 0u);
-  const uint32_t sc = __builtin_amdgcn_readfirstlane(S[a.scale]);
-  const uint32_t c0 = __builtin_amdgcn_readfirstlane(a.c0 >= 0 ? S[a.c0] : 0u);
-  const uint32_t c1 = __builtin_amdgcn_readfirstlane(a.c1 >= 0 ? S[a.c1] : 0u);
-  const uint64_t base = (uint64_t)c * SCAN_B + (uint64_t)threadIdx.x * SCAN_E;
-  const uint64_t nl = a.out_len;
-  uint32_t acc[16];
-  lc16_swar(a, cf, c0, c1, base, acc);
-  const uint32_t av = __builtin_amdgcn_readfirstlane(S[D.aslot]);
-  uint32_t pw[16];
-  pw[0] = 1;
-#pragma unroll
-  for (int j = 1; j < 16; j++) pw[j] = pw[j - 1] * av % HFP;
-  // the chunk's numerator coefficients num[base + k] (0 past nl), packed, and the thread's part of
-  // the chunk aggregate sum_{i > 0} num[i] a^i ((base + k) mod 16 = k)
-  uint32_t nb8[4] = {0, 0, 0, 0}, agg = 0;
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    const uint32_t v = base + k < nl ? hmod(hmod(acc[k]) * sc) : 0u;   // (acc <= 16 x 16 x 255 + 32)
-    nb8[k >> 2] |= v << (8 * (k & 3));
-    if (base + k > 0) agg += v * pw[k];
-  }
-  // publish the chunk aggregate
-  const uint32_t t = scan_block_sum(agg % HFP) % HFP;
-  if (threadIdx.x == 0)
-    __hip_atomic_store(fw + c, ((unsigned long long)epoch << 32) | t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // the aggregates of every later chunk (each word carries its own payload: no fence needed)
-  uint32_t carry = 0;
-  bool late = false;
-  for (int cb = c + 1 + (int)threadIdx.x; cb < D.nb; cb += SCAN_T) {
-    unsigned long long v = __hip_atomic_load(fw + cb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (uint32_t it = 0; (uint32_t)(v >> 32) != epoch; it++) {
-      if (it == (1u << 22)) { late = true; break; }
-      __builtin_amdgcn_s_sleep(1);
-      v = __hip_atomic_load(fw + cb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    carry += (uint32_t)v % HFP;
-  }
-  if (late) atomicOr(D.flag, SCAN_TIMEOUT);
-  uint32_t pw2[16], ipw[16];
-  div_powers(av, pw2, ipw);
-  lin_div_finish<SCAN_T, SCAN_E>(a, D, cf, sc, av, base, nl, nb8, pw2, ipw, carry % HFP);
-}
-
-// Round 5 in ONE launch with no waits (PLK_OPT_PROVE_EVAL_AGG): the scan's chunk aggregates are
+// Round 5 in ONE launch, no block waiting on another: the scan's chunk aggregates are
 // linear in the numerator's terms -- sum_{i in c} W[i] z^i = sc sum_t cf_t sum_{i in c} p_t[i] z^i
 // (W = sc sum_t cf_t p_t; the constants sit at i = 0, 1, in chunk 0, which is never a later chunk)
 // -- and round 4 already evaluates every term at z.  Its evaluation rows store each term's chunk
@@ -1233,16 +1106,13 @@ __global__ __launch_bounds__(SCAN_T) void lincomb_divide_kernel(LcBatch b, LinDi
 // their own; z(omega x) evaluated at z gives z_x's sums at z omega for the second division), so
 // this launch forms its chunk of both numerators in registers, reduces the later chunks' records
 // against the round-4 coefficients (one v_dot4 per 4 columns) and writes the quotient bytes: the
-// numerators are never stored and lin_scan_apply_kernel's launch is gone.  Extra grid rows run
-// the commitments that do not wait for round 5, as lincomb_scan_kernel's do.
+// numerators are never stored and the generic form's three launches (lincomb_batch,
+// lin_scan_sums_kernel, lin_scan_apply_kernel) are one.  Extra grid rows run the commitments that
+// do not wait for round 5 (EarlyMsm).
 struct AggMap {
   const uint8_t* agg;        // [chunk][16] column sums (prover memory, written by eval_kernel)
   int8_t col[2][LC_MAX];     // division d, numerator term t -> its agg column (-1: none)
 };
-// 512 threads of 8 coefficients per 4096-coefficient chunk: twice the waves of the 16-coefficient
-// form over the same ~770 chunks (one block each), so more of each block's load -> sum -> scan chain
-// overlaps (the chain, not the bytes, bounds this launch)
-constexpr int AGG_T = 512, AGG_E = SCAN_B / AGG_T;
 __global__ __launch_bounds__(AGG_T) void lincomb_agg_divide_kernel(LcBatch b, LinDivs L, const uint8_t* __restrict__ S,
                                                                   AggMap m, EarlyMsm em) {
   if ((int)blockIdx.y >= em.nd) {   // (uniform) an early commitment row
@@ -1305,7 +1175,7 @@ __global__ __launch_bounds__(AGG_T) void lincomb_agg_divide_kernel(LcBatch b, Li
     const uint32_t v = base + k < nl ? hmod(hmod(acc[k]) * sc) : 0u;   // (acc <= 16 x 16 x 255 + 32)
     nb8[k >> 2] |= v << (8 * (k & 3));
   }
-  lin_div_finish<AGG_T, AGG_E>(a, D, cf, sc, av, base, nl, nb8, pt, ipt, carry % HFP);
+  lin_div_finish(a, D, cf, sc, av, base, nl, nb8, pt, ipt, carry % HFP);
 }
 
 // (c) any other divisor: the reference's long division in one workgroup (only reached for
@@ -1481,9 +1351,9 @@ __global__ __launch_bounds__(PACK_T) void trim_pack_kernel(TrimArgs a, int nt, c
 
 // The commitments, the trimmed lengths and the packing in ONE launch (the prover's SRS in log
 // form, PLK_OPT_PROVE_PACK_FUSE): rows y < nrows of the grid are the log-form MSMs of arena rows
-// row0 + y (all 9, or only w_z and w_z_omega when the other 7 ran inside round 5's scan launch,
-// PLK_OPT_PROVE_EARLY_COMMITS); row nrows scans the trimmed-length buffers (block x < nt: buffer x, 4 KB per step from the
-// top; the vote buffer's block ORs its bytes) while the MSM rows stream.  Every finished record
+// row0 + y (all 9, or only w_z and w_z_omega when the other 7 ran inside round 5's division launch,
+// PLK_OPT_PROVE_EARLY_COMMITS); row nrows scans the trimmed-length buffers (block x < nt: buffer x,
+// 4 KB per step from the top; the vote buffer's block ORs its bytes) while the MSM rows stream.  Every finished record
 // and every trim block then arrives on `done`; the last arrival (one thread) packs the proof and
 // the status words into the mapped host buffer and writes the completion word, as
 // trim_pack_kernel does -- its launch and its scan latency leave the proof's tail.
@@ -1668,13 +1538,10 @@ struct plk_prover {
   uint64_t rem_blocks = 0;
   uint32_t* d_bsum = nullptr;      // scan block sums
   uint8_t* d_agg = nullptr;        // round 4's chunk aggregates of round 5's numerator terms [chunk][16]
-  unsigned long long* d_scanw = nullptr;   // lincomb_divide_kernel's chunk words {epoch, sum}
-  uint32_t scanw_stride = 0;       // words per division
-  uint32_t scan_epoch = 0;         // launches of lincomb_divide_kernel so far (0: none)
   PlkMsmResult* d_res = nullptr;   // 9 MSM records
   uint8_t* d_srs_log = nullptr;    // the SRS in log form (srs_log_kernel), valid when !srs_irregular
   const uint32_t* exp_words = nullptr;   // the group's EXP words on this prover's device
-  int early_rows = 0;              // commitments of this call already run by round 5's scan launch
+  int early_rows = 0;              // commitments of this call already run by round 5's division launch
   uint32_t* d_srs_flag = nullptr;  // srs_log_kernel's irregular flag
   uint32_t* d_done = nullptr;      // commit_pack_kernel's arrival word (re-armed by its last arrival)
   uint8_t* arena = nullptr;        // [9][cstride] committed polynomials
@@ -1887,7 +1754,7 @@ struct EvSpec {
   bool join = false;   // a further row of the previous entry's evaluation (no split, same out)
 };
 // agg_ok (optional): false when a row that stores chunk aggregates cannot be read in whole 16-byte
-// chunks (the aggregates are then not produced: the caller falls back to the two-launch scan)
+// chunks (the aggregates are then not produced: the caller takes round 5's generic form)
 EvArgs make_evargs(plk_prover* P, const std::vector<EvSpec>& ev, int post, bool* agg_ok = nullptr, uint8_t* agg = nullptr) {
   EvArgs a{};
   a.agg = agg;
@@ -1946,22 +1813,14 @@ EvArgs make_evargs(plk_prover* P, std::initializer_list<std::tuple<const uint8_t
   for (const auto& t : ev) v.push_back(EvSpec{std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t)});
   return make_evargs(P, v, post);
 }
-int evals_launch(plk_prover* P, const EvArgs& a, const EarlyMsm* em = nullptr) {
-  const int nrows = a.nr;
-  EarlyMsm e{};
-  if (em && em->nrows > 0) {
-    e = *em;
-    P->early_rows = e.nrows;
-  }
-  hipLaunchKernelGGL(eval_kernel, dim3(EV_BLOCKS, nrows + e.nrows), dim3(256), 0, P->st, a, P->d_S, P->d_tick, P->d_stat,
-                     e);
+int evals_launch(plk_prover* P, const EvArgs& a) {
+  hipLaunchKernelGGL(eval_kernel, dim3(EV_BLOCKS, a.nr), dim3(256), 0, P->st, a, P->d_S, P->d_tick, P->d_stat);
   PLK_HIP(hipGetLastError());
   return PLK_OK;
 }
-int evals(plk_prover* P, std::initializer_list<std::tuple<const uint8_t*, uint64_t, int, int>> ev, int post,
-          const EarlyMsm* em = nullptr) {
+int evals(plk_prover* P, std::initializer_list<std::tuple<const uint8_t*, uint64_t, int, int>> ev, int post) {
   const EvArgs a = make_evargs(P, ev, post);
-  return evals_launch(P, a, em);
+  return evals_launch(P, a);
 }
 
 int pmul(plk_prover* P, const uint8_t* a, uint64_t la, const uint8_t* b, uint64_t lb, uint8_t* out) {
@@ -2001,21 +1860,17 @@ struct LinDivReq {
   uint8_t* q;
   uint32_t* flag;
 };
-// lcs (optional): the numerators' lincombs, computed by the aggregate launch itself
-// am (optional, with lcs): the later chunks' aggregates from round 4's evaluation rows -- ONE launch
-int divide_linear(plk_prover* P, std::initializer_list<LinDivReq> reqs, const LcBatch* lcs = nullptr,
-                  const EarlyMsm* em = nullptr, const AggMap* am = nullptr) {
-  if (lcs) {   // a skipped (tiny) division would shift the numerators' order: compute them apart
-    int j = 0;
-    bool tiny = false;
-    for (const LinDivReq& r : reqs) tiny = tiny || r.nl < 2 || lcs->a[j++].out != r.num;
-    if (tiny) {
-      int rc = PLK_OK;
-      for (int i = 0; i < j && !rc; i++) rc = lincomb_batch(P, {lcs->a[i]});
-      if (rc) return rc;
-      lcs = nullptr;
-    }
-  }
+// Two forms.  Fused (fn): the numerators are never stored -- ONE lincomb_agg_divide_kernel launch
+// forms them from fn->lcs (a[i]: request i's numerator) and takes the later chunks' aggregates from
+// round 4's evaluation rows through fn->am; em (optional) adds the early commitment rows.  Both
+// divisions must be present (the map's rows are [W, ZZ]).  Generic (no fn): the numerators are in
+// memory; lin_scan_sums_kernel, then lin_scan_apply_kernel.
+struct FusedNums {
+  LcBatch lcs;
+  AggMap am;
+};
+int divide_linear(plk_prover* P, std::initializer_list<LinDivReq> reqs, const FusedNums* fn = nullptr,
+                  const EarlyMsm* em = nullptr) {
   LinDivs L{};
   int nd = 0, nbmax = 0;
   uint32_t* bs = P->d_bsum;
@@ -2030,33 +1885,25 @@ int divide_linear(plk_prover* P, std::initializer_list<LinDivReq> reqs, const Lc
     bs += nb + 2;
     nbmax = std::max(nbmax, nb);
   }
-  if (!nd) return PLK_OK;
-  if (lcs && plk_opt(PLK_OPT_PROVE_FUSE_DIV) && (uint32_t)nbmax <= P->scanw_stride) {
-    if (++P->scan_epoch == 0) ++P->scan_epoch;   // (words hold 0 after create: never a live epoch)
-    hipLaunchKernelGGL(lincomb_divide_kernel, dim3((unsigned)nbmax, nd), dim3(SCAN_T), 0, P->st, *lcs, L, P->d_S,
-                       P->d_scanw, P->scanw_stride, P->scan_epoch);
-    PLK_HIP(hipGetLastError());
-    return PLK_OK;
-  }
-  if (lcs) {
+  if (fn) {
+    if (nd != 2 || reqs.size() != 2 || fn->lcs.a[0].out != L.d[0].num || fn->lcs.a[1].out != L.d[1].num) {
+      plk_set_error("internal: fused round-5 division without both numerators");
+      return PLK_ERR_ARG;
+    }
     EarlyMsm e{};
-    e.nd = nd;
     if (em && em->nrows > 0) {
       e = *em;
-      e.nd = nd;
       e.X = std::min<uint32_t>(e.X, (uint32_t)nbmax);
       P->early_rows = e.nrows;
     }
-    if (am && nd == 2) {   // (both divisions present: the map's rows are [W, ZZ])
-      hipLaunchKernelGGL(lincomb_agg_divide_kernel, dim3((unsigned)nbmax, nd + (e.nrows > 0 ? e.nrows : 0)),
-                         dim3(AGG_T), 0, P->st, *lcs, L, P->d_S, *am, e);
-      PLK_HIP(hipGetLastError());
-      return PLK_OK;
-    }
-    hipLaunchKernelGGL(lincomb_scan_kernel, dim3((unsigned)nbmax, nd + (e.nrows > 0 ? e.nrows : 0)), dim3(SCAN_T), 0,
-                       P->st, *lcs, L, P->d_S, e);
+    e.nd = nd;
+    hipLaunchKernelGGL(lincomb_agg_divide_kernel, dim3((unsigned)nbmax, nd + e.nrows), dim3(AGG_T), 0, P->st, fn->lcs, L,
+                       P->d_S, fn->am, e);
+    PLK_HIP(hipGetLastError());
+    return PLK_OK;
   }
-  else hipLaunchKernelGGL(lin_scan_sums_kernel, dim3((unsigned)nbmax, nd), dim3(SCAN_T), 0, P->st, L, P->d_S);
+  if (!nd) return PLK_OK;
+  hipLaunchKernelGGL(lin_scan_sums_kernel, dim3((unsigned)nbmax, nd), dim3(SCAN_T), 0, P->st, L, P->d_S);
   PLK_HIP(hipGetLastError());
   // denominators poly_new({-z, 1}) and ({-z omega, 1}), src/plonk.h:604-613
   hipLaunchKernelGGL(lin_scan_apply_kernel, dim3((unsigned)nbmax, nd), dim3(SCAN_T), 0, P->st, L, P->d_S);
@@ -2155,7 +2002,6 @@ int create_on(const plk_plonk_desc_t* d, int dev, plk_prover_t** out) {
                o_stat = B.take(4 * NSTAT), o_tick = B.take(4 * TICK_STRIDE * (EV_MAX + 1)),
                o_rem = B.take(P->zh_len / 1024 + 64),
                o_bsum = B.take(4 * ((L.lw + SCAN_B - 1) / SCAN_B + 2) + 4 * ((L.lzz + SCAN_B) / SCAN_B + 2)),
-               o_scanw = B.take(8 * 2 * ((std::max(L.lw, L.lzz) + SCAN_B) / SCAN_B + 2)),
                o_agg = B.take(16 * ((std::max(L.lw, L.lzz) + SCAN_B) / SCAN_B + 2)),
                o_res = B.take(9 * sizeof(PlkMsmResult)),
                o_srslog = B.take(P->srs_len + 16), o_words = B.take(64),
@@ -2190,9 +2036,7 @@ int create_on(const plk_plonk_desc_t* d, int dev, plk_prover_t** out) {
   uint8_t* m = P->mem;
   P->d_srs = m + o_srs; P->d_zh = m + o_zh; P->d_h3 = m + o_h3; P->d_hinv = m + o_hinv; P->d_S = m + o_S;
   P->d_stat = (uint32_t*)(m + o_stat); P->d_tick = (uint32_t*)(m + o_tick); P->d_rem = m + o_rem; P->d_bsum = (uint32_t*)(m + o_bsum);
-  P->d_scanw = (unsigned long long*)(m + o_scanw);
   P->d_agg = m + o_agg;
-  P->scanw_stride = (uint32_t)((std::max(L.lw, L.lzz) + SCAN_B) / SCAN_B + 2);
   P->d_res = (PlkMsmResult*)(m + o_res); P->arena = m + o_arena;
   P->d_srs_log = m + o_srslog;
   P->d_srs_flag = (uint32_t*)(m + o_words);
@@ -2542,38 +2386,37 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
   // r(x) is never materialised: r_z comes from its terms' evaluations (scalars_r4) and w_z(x)
   // takes v r(x) term by term.  One launch: the 14 evaluations + rounds 4/5 scalar programs.
   // the 7 commitments that do not wait for round 5 (a b c z t_lo t_mid t_hi) as extra grid rows of
-  // this launch (PLK_OPT_PROVE_EARLY_COMMITS = 2) or of round 5's scan launch (= 1); log-form SRS
-  // and the fused packing only -- commit_pack_kernel then runs w_z, w_z_omega and packs
+  // round 5's fused division launch (PLK_OPT_PROVE_EARLY_COMMITS); log-form SRS and the fused
+  // packing only -- commit_pack_kernel then runs w_z, w_z_omega and packs
   P->early_rows = 0;
-  const int64_t early = !P->srs_irregular && plk_opt(PLK_OPT_PROVE_SRS_LOGS) && plk_opt(PLK_OPT_PROVE_PACK_FUSE)
-                            ? plk_opt(PLK_OPT_PROVE_EARLY_COMMITS)
-                            : 0;
+  const bool early = !P->srs_irregular && plk_opt(PLK_OPT_PROVE_SRS_LOGS) && plk_opt(PLK_OPT_PROVE_PACK_FUSE) &&
+                     plk_opt(PLK_OPT_PROVE_EARLY_COMMITS);
   const MsmRowLens rl = msm_row_lens(P, L);
   const EarlyMsm em{P->d_srs_log, P->arena, (uint64_t)P->cstride, rl, P->d_res, P->exp_words, 7, 0, (uint32_t)(2048 / 9)};
-  // round 5's numerators (built here: with PLK_OPT_PROVE_EVAL_AGG round 4's evaluation rows also
-  // store their terms' scan-chunk aggregates, lincomb_agg_divide_kernel)
-  LcBatch nb5{};
+  // round 5's numerators (built here: in the fused form round 4's evaluation rows also store their
+  // terms' scan-chunk aggregates, lincomb_agg_divide_kernel)
+  FusedNums nb5{};
   // w_z(x)'s numerator terms, in agg column order (column t = term t): t_lo t_mid t_hi q_m q_l q_r
   // q_o z_x P3 a_x b_x c_x s_sigma_1 s_sigma_2; column 14 = z(omega x) at z = z_x at z omega
   enum { AC_TLO, AC_TMID, AC_THI, AC_QM, AC_QL, AC_QR, AC_QO, AC_ZX, AC_P3, AC_A, AC_B, AC_C, AC_S1, AC_S2, AC_ZW };
-  nb5.a[0] = make_lc({{cTlo, std::min<uint64_t>(part, L.ltx)}, {cTmid, lmid}, {cThi, lhi}, {QM, n}, {QL, n},
-                      {QR, n}, {QO, n}, {cZ, L.lzx}, {P->P3, L.lr3}, {cA, L.la}, {cB, L.la}, {cC, L.la}, {S1, n},
-                      {S2, n}},
-                     {S_ONE, S_ZN2, S_Z2N4, S_VAB, S_VAZ, S_VBZ, S_VCZ, S_VR24, S_VR3B, S_V2, S_V3, S_V4, S_V5,
-                      S_V6},
-                     S_W0, -1, S_ONE, -1, P->W, L.lw);
-  nb5.a[1] = make_lc({{cZ, L.lzx}}, {S_ONE}, S_NEGZWZ, -1, S_ONE, -1, P->ZZ, L.lzz);
-  // fused numerators need 16-byte aligned terms readable in whole 16-byte chunks: the
-  // caller's polynomials (length n) qualify when n % 16 == 0 and they are aligned
-  bool fuse = n % 16 == 0 && nb5.a[0].nt > 0 && nb5.a[1].nt > 0;
+  LcArgs* const num5 = nb5.lcs.a;   // [0]: W, [1]: ZZ
+  num5[0] = make_lc({{cTlo, std::min<uint64_t>(part, L.ltx)}, {cTmid, lmid}, {cThi, lhi}, {QM, n}, {QL, n},
+                     {QR, n}, {QO, n}, {cZ, L.lzx}, {P->P3, L.lr3}, {cA, L.la}, {cB, L.la}, {cC, L.la}, {S1, n},
+                     {S2, n}},
+                    {S_ONE, S_ZN2, S_Z2N4, S_VAB, S_VAZ, S_VBZ, S_VCZ, S_VR24, S_VR3B, S_V2, S_V3, S_V4, S_V5,
+                     S_V6},
+                    S_W0, -1, S_ONE, -1, P->W, L.lw);
+  num5[1] = make_lc({{cZ, L.lzx}}, {S_ONE}, S_NEGZWZ, -1, S_ONE, -1, P->ZZ, L.lzz);
+  // the fused form needs both divisions, and 16-byte aligned terms readable in whole 16-byte
+  // chunks: the caller's polynomials (length n) qualify when n % 16 == 0 and they are aligned;
+  // make_evargs has the last word (agg_ok), row by row
+  bool fuse = n % 16 == 0 && num5[0].nt > 0 && num5[1].nt > 0 && L.lw >= 2 && L.lzz >= 2;
   for (int j = 0; j < 2; j++) {
-    fuse = fuse && (uintptr_t)nb5.a[j].out % 16 == 0;
-    for (int t = 0; t < nb5.a[j].nt; t++) fuse = fuse && (uintptr_t)nb5.a[j].p[t] % 16 == 0;
+    fuse = fuse && (uintptr_t)num5[j].out % 16 == 0;
+    for (int t = 0; t < num5[j].nt; t++) fuse = fuse && (uintptr_t)num5[j].p[t] % 16 == 0;
   }
-  bool agg = fuse && P->d_agg && plk_opt(PLK_OPT_PROVE_EVAL_AGG) && !plk_opt(PLK_OPT_PROVE_FUSE_DIV) &&
-             L.lw >= 2 && L.lzz >= 2;
   EvArgs ea{};
-  if (agg) {   // t(z) from its three slices (x^(n + 2), x^(2n + 4): their offsets), every W term's chunks
+  if (fuse) {   // t(z) from its three slices (x^(n + 2), x^(2n + 4): their offsets), every W term's chunks
     const int m1 = (int)(part % 16), m2 = (int)(2 * part % 16);
     ea = make_evargs(P,
                      {{cA, L.la, S_Z, S_AZ, AC_A}, {cB, L.la, S_Z, S_BZ, AC_B}, {cC, L.la, S_Z, S_CZ, AC_C},
@@ -2583,31 +2426,30 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
                       {P->ZW, L.lzw, S_Z, S_ZWZ, AC_ZW}, {L1, n, S_Z, S_L1Z},
                       {QM, n, S_Z, S_QMZ, AC_QM}, {QL, n, S_Z, S_QLZ, AC_QL}, {QR, n, S_Z, S_QRZ, AC_QR},
                       {QO, n, S_Z, S_QOZ, AC_QO}, {cZ, L.lzx, S_Z, S_ZXZ, AC_ZX}, {P->P3, L.lr3, S_Z, S_P3Z, AC_P3}},
-                     EV_POST_R4, &agg, P->d_agg);
+                     EV_POST_R4, &fuse, P->d_agg);
   }
-  if (!agg)
+  if (!fuse)
     ea = make_evargs(P, {{cA, L.la, S_Z, S_AZ}, {cB, L.la, S_Z, S_BZ}, {cC, L.la, S_Z, S_CZ}, {S1, n, S_Z, S_S1Z},
                          {S2, n, S_Z, S_S2Z}, {P->TX, L.ltx, S_Z, S_TZ}, {P->ZW, L.lzw, S_Z, S_ZWZ}, {L1, n, S_Z, S_L1Z},
                          {QM, n, S_Z, S_QMZ}, {QL, n, S_Z, S_QLZ}, {QR, n, S_Z, S_QRZ}, {QO, n, S_Z, S_QOZ},
                          {cZ, L.lzx, S_Z, S_ZXZ}, {P->P3, L.lr3, S_Z, S_P3Z}},
                      EV_POST_R4);
-  RC(evals_launch(P, ea, early == 2 ? &em : nullptr));
+  RC(evals_launch(P, ea));
   // ---- round 5: opening polynomials (src/plonk.h:580-621)
-  // w_z numerator and z(x) - z_omega_z, then both divisions: one launch with the aggregates of
-  // round 4, else each pair in one launch per phase
-  {
-    AggMap am{};
-    if (agg) {
-      am.agg = P->d_agg;
-      for (int t = 0; t < LC_MAX; t++) am.col[0][t] = am.col[1][t] = -1;
-      for (int t = 0; t < nb5.a[0].nt; t++) am.col[0][t] = (int8_t)t;   // (AC_* order)
-      am.col[1][0] = AC_ZW;
-    }
-    if (!fuse) RC(lincomb_batch(P, {nb5.a[0], nb5.a[1]}));
-    RC(divide_linear(P, {{P->W, L.lw, S_Z, cWz, P->d_stat + ST_REM_W1},
-                         {P->ZZ, L.lzz, S_ZOMEGA, cWzw, P->d_stat + ST_REM_W2}},
-                     fuse ? &nb5 : nullptr, early == 1 ? &em : nullptr, agg ? &am : nullptr));
+  // w_z numerator and z(x) - z_omega_z, then both divisions.  Fused: one launch with the aggregates
+  // of round 4 (and the early commitment rows).  Generic: the numerators by lincomb_batch, then the
+  // scan's sums and apply launches
+  if (fuse) {
+    nb5.am.agg = P->d_agg;
+    for (int t = 0; t < LC_MAX; t++) nb5.am.col[0][t] = nb5.am.col[1][t] = -1;
+    for (int t = 0; t < num5[0].nt; t++) nb5.am.col[0][t] = (int8_t)t;   // (AC_* order)
+    nb5.am.col[1][0] = AC_ZW;
+  } else {
+    RC(lincomb_batch(P, {num5[0], num5[1]}));
   }
+  RC(divide_linear(P, {{P->W, L.lw, S_Z, cWz, P->d_stat + ST_REM_W1},
+                       {P->ZZ, L.lzz, S_ZOMEGA, cWzw, P->d_stat + ST_REM_W2}},
+                   fuse ? &nb5 : nullptr, early ? &em : nullptr));
   // ---- trimmed lengths for the reference's exits: computed by the packing kernel after the MSM
   TrimArgs trims{};
   int ntrims = 0;
@@ -2667,10 +2509,6 @@ int check_status(const plk_prover* P, const uint32_t* st, int strict, int circui
   if (st[ST_TXLEN] <= 2 * part) { plk_set_error("Invalid slice indices in poly_slice"); return PLK_ERR_RANGE; }
   for (int i = 4; i < 7; i++)
     if (st[ST_LEN0 + i] > P->srs_len) { plk_set_error("SRS length is less than polynomial length"); return PLK_ERR_RANGE; }
-  if ((st[ST_REM_W1] | st[ST_REM_W2]) & SCAN_TIMEOUT) {   // (lincomb_divide_kernel: a wait gave up)
-    plk_set_error("internal: round-5 division scan timed out waiting for a chunk aggregate");
-    return PLK_ERR_HIP;
-  }
   if (strict && st[ST_REM_W1]) { plk_set_error("assertion poly_is_zero(&rem1) failed"); return PLK_ERR_ARG; }
   if (strict && st[ST_REM_W2]) { plk_set_error("assertion poly_is_zero(&rem2) failed"); return PLK_ERR_ARG; }
   for (int i = 7; i < 9; i++)
@@ -2862,13 +2700,12 @@ int plk_prover_launches(plk_prover_t* P, const uint8_t* const d_polys[13], const
   if (P->nhelp) { plk_set_error("plk_prover_launches: a prover with helpers attached"); return PLK_ERR_ARG; }
   PROVER_ON_DEVICE(P);
   PLK_HIP(hipStreamSynchronize(P->st));
-  const uint32_t epoch = P->scan_epoch, seq = P->seq;
+  const uint32_t seq = P->seq;
   PLK_HIP(hipStreamBeginCapture(P->st, hipStreamCaptureModeThreadLocal));
   int rc = rounds(P, d_polys, chal, rand9, (flags & PLK_PROVE_PREPROCESSED) != 0);
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(P->st, &g);
-  P->seq = seq;   // (nothing ran: the next call's completion word and scan epochs are unchanged)
-  P->scan_epoch = epoch;
+  P->seq = seq;   // (nothing ran: the next call's completion word is unchanged)
   if (!rc && (e != hipSuccess || !g)) {
     plk_set_error("plk_prover_launches: stream capture failed (%s)", hipGetErrorString(e));
     rc = PLK_ERR_HIP;

@@ -18,18 +18,18 @@ buffers -- Z_H's copy, the commitment arena, every intermediate -- are 16-byte a
           4-byte aligned.  Else lincomb_batch({num}) (one launch either way), divide_zh
           (divide_binomial4_kernel when n % 4 == 0, else divide_binomial_kernel: one launch),
           copy3_kernel.
-  fuse5   round 5's numerators computed inside the division launch: n % 16 == 0 and q_m q_l q_r q_o
-          s_sigma_1 s_sigma_2 16-byte aligned.  Else a lincomb_batch of 2 first (one launch when those
-          six are aligned, else 2) and the two-launch scan (lin_scan_sums_kernel, lin_scan_apply_kernel).
-          With fuse5: one launch with PROVE_FUSE_DIV (lincomb_divide_kernel) or with agg
-          (lincomb_agg_divide_kernel), else lincomb_scan_kernel + lin_scan_apply_kernel.
-  agg     round 4's evaluation rows store the chunk aggregates: fuse5, PROVE_EVAL_AGG and not
-          PROVE_FUSE_DIV (every aggregated caller row is then aligned with n % 16 == 0: vec == 2).
+  fuse5   round 5's numerators computed inside the division launch, ONE launch
+          (lincomb_agg_divide_kernel): n % 16 == 0 and q_m q_l q_r q_o s_sigma_1 s_sigma_2 16-byte
+          aligned.  Else a lincomb_batch of 2 first (one launch when those six are aligned, else 2) and
+          the two-launch scan (lin_scan_sums_kernel, lin_scan_apply_kernel).  No option is involved.
+  agg     round 4's evaluation rows store the chunk aggregates: exactly with fuse5 (every aggregated
+          caller row is then aligned with n % 16 == 0: vec == 2, so make_evargs' agg_ok holds).
   vec     per evaluated caller polynomial (s_sigma_1 s_sigma_2 l_1 q_m q_l q_r q_o): 0 bytes, 1 aligned
           (the tail of the last 16-byte load masked), 2 aligned and n % 16 == 0.
 
 The round-3 products (their NTT pass launches), the evaluation launch and the commitments depend
-on lengths and options only, so they cancel in launch_delta.
+on lengths and options only, so they cancel in launch_delta; no option moves a switch listed
+above, so the `options` arguments below change nothing (the GPU file passes the sets it runs).
 """
 import numpy as np
 
@@ -38,14 +38,7 @@ NAMES = ("f_a", "f_b", "f_c", "q_o", "q_m", "q_l", "q_r", "q_c", "s1", "s2", "s3
 PREP_INPUTS = (FA, FB, FC, ACC, S1, S2, S3)
 FUSE5_INPUTS = (QM, QL, QR, QO, S1, S2)
 EVAL_INPUTS = (S1, S2, L1, QM, QL, QR, QO)
-DEFAULTS = {"PROVE_EVAL_AGG": 1, "PROVE_FUSE_DIV": 0}
 ALIGNED = (0,) * 13
-
-
-def _opts(options):
-    o = dict(DEFAULTS)
-    o.update(options or {})
-    return o
 
 
 def _al(residues, idx, m=16):
@@ -54,14 +47,13 @@ def _al(residues, idx, m=16):
 
 def variants(n, residues, options=None):
     """{prep, numdiv, fuse5, agg} of rounds() at n gates for the 13 address residues (mod 16, in
-    d_polys order) under `options` (PROVE_EVAL_AGG, PROVE_FUSE_DIV; the others move no switch)"""
+    d_polys order); `options` move no switch"""
     assert len(residues) == 13
-    o = _opts(options)
     la, lzx = n + 2, n + 3
     prep = _al(residues, PREP_INPUTS) and la <= lzx <= la + 1
     numdiv = n % 4 == 0 and residues[QC] % 4 == 0
     fuse5 = n % 16 == 0 and _al(residues, FUSE5_INPUTS)
-    agg = fuse5 and bool(o["PROVE_EVAL_AGG"]) and not o["PROVE_FUSE_DIV"]
+    agg = fuse5
     return dict(prep=prep, numdiv=numdiv, fuse5=fuse5, agg=agg)
 
 
@@ -73,7 +65,6 @@ def vec_modes(n, residues):
 def switched_launches(n, residues, options=None):
     """kernel launches of the parts of rounds() that depend on the placement"""
     v = variants(n, residues, options)
-    o = _opts(options)
     k = 0
     if v["prep"]:
         k += 1                                              # prep_kernel
@@ -83,13 +74,11 @@ def switched_launches(n, residues, options=None):
         k += 1                                              # z_x
         k += 1 if _al(residues, (S1, S2, S3)) else 8        # round 3's linear factors
     k += 1 if v["numdiv"] else 3                            # numdiv | lincomb, divide, copy3
-    if not v["fuse5"]:
+    if v["fuse5"]:
+        k += 1                                              # lincomb_agg_divide
+    else:
         k += 1 if _al(residues, FUSE5_INPUTS) else 2        # W and ZZ numerators
         k += 2                                              # lin_scan_sums, lin_scan_apply
-    elif o["PROVE_FUSE_DIV"] or v["agg"]:
-        k += 1                                              # lincomb_divide | lincomb_agg_divide
-    else:
-        k += 2                                              # lincomb_scan, lin_scan_apply
     return k
 
 
@@ -152,12 +141,11 @@ def placements(n):
     return (SINGLE if n in SINGLE_SIZES else []) + TOGETHER + MIXES
 
 
-# the option combinations of test_round5_divisions_vs_oracle (FUSE_DIV, EVAL_AGG, EARLY_COMMITS) ...
-DIVISION_OPTIONS = [dict(PROVE_FUSE_DIV=f, PROVE_EVAL_AGG=a, PROVE_EARLY_COMMITS=e)
-                    for f, a, e in ((1, 0, 1), (0, 1, 1), (0, 0, 1), (0, 1, 2), (0, 1, 0), (1, 1, 1))]
+# the option values of test_round5_divisions_vs_oracle (EARLY_COMMITS) ...
+DIVISION_OPTIONS = [dict(PROVE_EARLY_COMMITS=e) for e in (1, 0)]
 # ... of test_commitments_srs_log_form (SRS_LOGS, PACK_FUSE, EARLY_COMMITS) ...
 COMMIT_OPTIONS = [dict(PROVE_SRS_LOGS=s, PROVE_PACK_FUSE=p, PROVE_EARLY_COMMITS=e)
-                  for s, p, e in ((1, 1, 0), (1, 1, 2), (1, 0, 1), (0, 1, 1))]
+                  for s, p, e in ((1, 1, 0), (1, 0, 1), (0, 1, 1))]
 # ... and of test_derive_t2a_modes_vs_oracle
 DERIVE_OPTIONS = [dict(PROVE_DERIVE_T2A=m) for m in (0, 1, 2)]
 OPTION_SETS = DIVISION_OPTIONS + COMMIT_OPTIONS + DERIVE_OPTIONS

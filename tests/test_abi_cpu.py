@@ -87,23 +87,24 @@ def test_options_without_gpu():
                 "NTT_SHARE": 1, "NTT_SHARED_FIX": 1, "NTT_T13_MIN_K": 21, "NTT_CENTER_BLOCKS": 0,
                 "MSM_HALF": 1, "MSM_SHARD_MIN": 1 << 16, "NTT_CENTER_SUM": 1, "MSM_HOST_LANES": 4,
                 "PROVE_DERIVE_T2A": 2, "NTT_TABLE_SHARE": 1, "NTT_LAUNCH_LOG": 0,
-                "PROVE_FUSE_DIV": 0, "PROVE_SRS_LOGS": 1, "PROVE_PACK_FUSE": 1, "PROVE_EARLY_COMMITS": 1,
-                "PROVE_EVAL_AGG": 1}
+                "PROVE_SRS_LOGS": 1, "PROVE_PACK_FUSE": 1, "PROVE_EARLY_COMMITS": 1}
     for k, v in defaults.items():
         assert h.get_option(k) == v, k
     with h.options(NTT_SHARED_FIX=2, POLY_BLOCK_L=4096, POLY_BLOCK_S=513):
         assert h.get_option("NTT_SHARED_FIX") == 2 and h.get_option("POLY_BLOCK_S") == 513
     assert h.get_option("NTT_SHARED_FIX") == 1 and h.get_option("POLY_BLOCK_L") == 0
-    for k, v in (("NTT_SHARED_FIX", 3), ("NTT_T13_MIN_K", 12), ("POLY_BLOCK_S", 3670017), (99, 0), (0, 0)):
+    for k, v in (("NTT_SHARED_FIX", 3), ("NTT_T13_MIN_K", 12), ("POLY_BLOCK_S", 3670017),
+                 ("PROVE_EARLY_COMMITS", 2), (99, 0), (0, 0)):
         with pytest.raises(h.PlonkHipError) as e:
             h.set_option(k, v)
         assert e.value.code == h.PLK_ERR_ARG
     assert h.get_option(99) == -1
-    assert 27 not in h.OPTIONS.values()    # number 27 is retired: no name, never set, reads as unknown
-    with pytest.raises(h.PlonkHipError) as e:
-        h.set_option(27, 0)
-    assert e.value.code == h.PLK_ERR_ARG
-    assert h.get_option(27) == -1
+    for num in (21, 26, 27):    # retired numbers: no name, never set, read as unknown
+        assert num not in h.OPTIONS.values()
+        with pytest.raises(h.PlonkHipError) as e:
+            h.set_option(num, 0)
+        assert e.value.code == h.PLK_ERR_ARG
+        assert h.get_option(num) == -1
     csrc = os.path.join(PKG, "csrc")
     envs = set()
     for f in os.listdir(csrc):

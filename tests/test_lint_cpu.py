@@ -15,7 +15,7 @@ CSRC = os.path.join(ROOT, "plonk.c_amd", "csrc")
 # a hex constant with 0xFF bytes separated by zero bytes (0x00FF00FF, 0xFF00FF): byte lanes.  Contiguous
 # masks (0xFF, 0xFFFF, 0xFFFF0000) select one field and do not match.
 LANE_MASK = re.compile(r"0x0*ff(?:00)+ff(?:00|ff)*u?\b", re.IGNORECASE)
-# a product: `*` or the 24-bit multiply intrinsics (round 4's first lc16_swar had the mask inside
+# a product: `*` or the 24-bit multiply intrinsics (round 4's first lc_swar had the mask inside
 # __umul24 and passed a `*`-only check; it now goes through prove.hip's lanes02 / lanes13, whose
 # empty asm keeps the combine from seeing the mask)
 MUL = re.compile(r"\*|__u?mul24|__builtin_amdgcn_mul_u?24")

@@ -287,14 +287,14 @@ def test_srs_boundary_every_case(hip, oracle, n, seed):
     assert not bad, bad
 
 
-FORMS = [(1, 1, 1), (1, 1, 0), (1, 1, 2), (1, 0, 1), (0, 1, 1)]   # (SRS_LOGS, PACK_FUSE, EARLY_COMMITS)
+FORMS = [(1, 1, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1)]   # (SRS_LOGS, PACK_FUSE, EARLY_COMMITS)
 
 
 @pytest.mark.parametrize("n,seed", SIZES)
 @pytest.mark.parametrize("form", FORMS)
 def test_srs_boundary_commitment_forms(hip, oracle, n, seed, form):
-    """The same pair under each commitment form -- log form fused (early commitments in the scan
-    launch, in none, in round 4's), log form unfused, G1 form -- plain and preprocessed"""
+    """The same pair under each commitment form -- log form fused (early commitments in round 5's
+    division launch, or in none), log form unfused, G1 form -- plain and preprocessed"""
     I = _instance(oracle, n, seed)
     bad = {}
     with hip.options(PROVE_SRS_LOGS=form[0], PROVE_PACK_FUSE=form[1], PROVE_EARLY_COMMITS=form[2]):
@@ -363,17 +363,21 @@ def test_strict_accept_and_single_coefficient(hip, oracle, n, seed):
 
 @pytest.mark.parametrize("n,seed", STRICT_SIZES)
 def test_strict_accept_every_division_form(hip, oracle, n, seed):
-    """The strict accept where the round-5 remainder words come from other kernels: the look-back
-    division, the two-launch division, a preprocessed circuit, and the split proof
+    """The strict accept where the round-5 remainder words come from other kernels: the generic
+    two-launch division (q_m at an odd address, twice), a preprocessed circuit, and the split proof
     (chains_dev + rounds_ext_dev, both chains)"""
     c = _strict_case(oracle, n, seed)
     pr = hip.Prover(n, c["zh"], c["pts"])
     d = _dev(c["polys"])
     chal, rnd, want = c["chal"], c["rnd"], c["want"].hex()
-    for opt in ({"PROVE_FUSE_DIV": 1}, {"PROVE_EVAL_AGG": 0}):
-        with hip.options(**opt):
-            for _ in range(2):
-                assert pr.rounds_dev(d, chal, rnd, strict=True).hex() == want, opt
+    # q_m at an odd address: round 5's numerators by lincomb_batch, then the two-launch scan
+    backing = torch.zeros(n + 16, dtype=torch.uint8, device="cuda")
+    backing[3:3 + n] = d[QM]
+    odd = list(d)
+    odd[QM] = backing[3:3 + n]
+    assert odd[QM].data_ptr() % 16 == 3
+    for _ in range(2):
+        assert pr.rounds_dev(odd, chal, rnd, strict=True).hex() == want, "q_m at an odd address"
     pr.preprocess(d)
     assert pr.rounds_dev(d, chal, rnd, strict=True, preprocessed=True).hex() == want
     pr.preprocess(None)

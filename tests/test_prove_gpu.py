@@ -59,14 +59,30 @@ def _synthetic(n, seed, srs_len):
     return gen.prove_instance(n, seed, srs_len)
 
 
+QM = 4   # q_m's place among the 13 polynomials
+
+
+def _odd_qm(dev, off=3):
+    """the same 13 device polynomials with q_m handed over as a view at an odd address (`off` past
+    a 16-byte boundary) inside a larger buffer -- the other twelve are not copied: round 5 cannot fuse its numerators and takes the generic form (lincomb_batch,
+    lin_scan_sums_kernel, lin_scan_apply_kernel) at any n"""
+    n = dev[QM].numel()
+    backing = torch.zeros(n + 16, dtype=torch.uint8, device="cuda")
+    backing[off:off + n] = dev[QM]
+    odd = list(dev)
+    odd[QM] = backing[off:off + n]
+    assert off % 2 == 1 and odd[QM].data_ptr() % 16 == off
+    torch.cuda.synchronize()      # (the prover runs on its own stream)
+    return odd
+
+
 @pytest.mark.parametrize("n,seed,z", [(256, 61, 0), (256, 62, 1), (4096, 63, 0), (16384, 61, 0), (16384, 64, 0),
                                       (16384, 65, None), (65536, 61, 0), (65536, 67, 16)])
 def test_round5_divisions_vs_oracle(hip, oracle, n, seed, z):
-    """Round 5's numerators and divisions by x - z, x - z omega: the one-launch forms -- the
-    chunk aggregates from round 4's evaluation rows (PROVE_EVAL_AGG = 1, the default:
-    lincomb_agg_divide_kernel, with the early commitments in its grid, in round 4's, or in neither)
-    and the look-back form (PROVE_FUSE_DIV = 1, lincomb_divide_kernel: chunks in reverse block
-    order, each waiting for the later chunks' aggregates) -- and the two-launch form give the
+    """Round 5's numerators and divisions by x - z, x - z omega in both forms: fused (aligned
+    inputs: the chunk aggregates from round 4's evaluation rows, one lincomb_agg_divide_kernel
+    launch, with the early commitments in its grid or not) and generic (q_m at an odd address: the
+    numerators by lincomb_batch, then lin_scan_sums_kernel and lin_scan_apply_kernel) give the
     oracle's proof, from 1 to ~32 chunks per division.  z = 0 is the shift q[j] = num[j + 1], which
     crosses lanes, waves and chunks (src/poly.h:124-177 with divisor x - 0)."""
     polys, chal, rnd, zh, pts = _synthetic(n, seed, 2 * n + 8)
@@ -79,28 +95,35 @@ def test_round5_divisions_vs_oracle(hip, oracle, n, seed, z):
         want = RefProver(oracle, pts.tobytes(), n, z_h=zh.tobytes()).rounds(polys, chal, rnd, strict=False)
     except ProveError:   # (16384, 64, 0): t(x) too short for its slices -- the reference exits there too
         want = None
-    for fuse, agg, early in ((1, 0, 1), (0, 1, 1), (0, 0, 1), (0, 1, 2), (0, 1, 0), (1, 1, 1), (0, 1, 1)):
-        with hip.options(PROVE_FUSE_DIV=fuse, PROVE_EVAL_AGG=agg, PROVE_EARLY_COMMITS=early):
-            if want is None:
-                with pytest.raises(hip.PlonkHipError):
-                    pr.rounds_dev(dev, chal, rnd, strict=False)
-            else:
-                assert pr.rounds_dev(dev, chal, rnd, strict=False).hex() == want.hex(), (fuse, agg, early)
+    odd = _odd_qm(dev)
+
+    def check(d, what):
+        if want is None:
+            with pytest.raises(hip.PlonkHipError):
+                pr.rounds_dev(d, chal, rnd, strict=False)
+        else:
+            assert pr.rounds_dev(d, chal, rnd, strict=False).hex() == want.hex(), what
+
+    for early in (1, 0):
+        with hip.options(PROVE_EARLY_COMMITS=early):
+            check(dev, ("fused", early))
+            check(odd, ("generic", early))
+    check(dev, "defaults")
 
 
 @pytest.mark.parametrize("n,seed", [(37, 71), (4096, 72), (20000, 73)])
 def test_commitments_srs_log_form(hip, oracle, n, seed):
     """The 9 commitments from the SRS in log form (PROVE_SRS_LOGS = 1: srs_log_kernel once at
     create; per proof commit_pack_kernel -- commitments, trimmed lengths and packing in one
-    launch, with or without the 7 commitments that do not wait for round 5 running inside its scan
-    launch -- or msm_log_kernel + trim_pack_kernel; committed lengths n + 2 .. n + 3, so 16-point
+    launch, with or without the 7 commitments that do not wait for round 5 running inside its
+    division launch -- or msm_log_kernel + trim_pack_kernel; committed lengths n + 2 .. n + 3, so 16-point
     groups plus a ragged tail) and from the G1 form give the oracle's proof, and the strict
     rejection (its status words) is the same in every form."""
     polys, chal, rnd, zh, pts = _synthetic(n, seed, 2 * n + 8)
     want = RefProver(oracle, pts.tobytes(), n, z_h=zh.tobytes()).rounds(polys, chal, rnd, strict=False)
     pr = hip.Prover(n, zh, pts)
     dev = [torch.from_numpy(p).to("cuda") for p in polys]
-    for logs, fuse, early in ((1, 1, 1), (1, 1, 0), (1, 1, 2), (1, 0, 1), (0, 1, 1), (1, 1, 1)):
+    for logs, fuse, early in ((1, 1, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1)):
         with hip.options(PROVE_SRS_LOGS=logs, PROVE_PACK_FUSE=fuse, PROVE_EARLY_COMMITS=early):
             assert pr.rounds_dev(dev, chal, rnd, strict=False).hex() == want.hex(), (logs, fuse, early)
             with pytest.raises(hip.PlonkHipError, match="remainder"):
@@ -418,26 +441,30 @@ def test_preprocessed_tensors_held_and_overwrite_needs_preprocess(hip):
 # every switch that changes how a 2^20 proof is computed, one at a time away from its default
 _SWEEP = [("NTT_F29", 0), ("NTT_SHARE", 0), ("NTT_SHARED_FIX", 0), ("NTT_SHARED_FIX", 2), ("NTT_CENTER_BLOCKS", 768),
           ("NTT_CENTER_SUM", 0), ("NTT_TABLE_SHARE", 0), ("PROVE_DERIVE_T2A", 0), ("PROVE_DERIVE_T2A", 1),
-          ("PROVE_FUSE_DIV", 1), ("PROVE_SRS_LOGS", 0), ("PROVE_PACK_FUSE", 0), ("PROVE_EARLY_COMMITS", 0),
-          ("PROVE_EARLY_COMMITS", 2), ("PROVE_EVAL_AGG", 0), ("PROVE_SYNC", 1)]
+          ("PROVE_SRS_LOGS", 0), ("PROVE_PACK_FUSE", 0), ("PROVE_EARLY_COMMITS", 0), ("PROVE_SYNC", 1)]
 
 
 def test_option_sweep_2_20_vs_golden(hip):
     """Config C5 with each computation switch (PLK_OPT_*) moved off its default in turn -- BabyBear
     instead of F29, no shared operands, the shared-operand pass off / forced, another centre grid,
-    no centre sum groups, per-array column reads, A2 B2 as a product or its own kernel, the fused
-    look-back division, G1-form commitments, unfused packing, the early commitments elsewhere, the
-    two-launch division, stream-synchronised completion -- plain and preprocessed:
-    the golden bytes every time (round 5 found a wrong-result bug behind a non-default option)."""
+    no centre sum groups, per-array column reads, A2 B2 as a product or its own kernel, G1-form
+    commitments, unfused packing, the early commitments with the other two, stream-synchronised
+    completion -- plain and preprocessed: the golden bytes every time (round 5 found a wrong-result
+    bug behind a non-default option).  Round 5's generic form (lincomb_batch and the two-launch
+    scan) is no option: it is reached by q_m at an odd address, plain and preprocessed."""
     g = load_golden("prove_2_20.json")
     n = g["n"]
     polys, chal, rnd, zh, pts = _synthetic(n, g["seed"], g["srs_len"])
     pr = hip.Prover(n, zh, pts)
     dev = [torch.from_numpy(p).to("cuda") for p in polys]
+    odd = _odd_qm(dev)
     for opt, val in _SWEEP:
         with hip.options(**{opt: val}):
             assert pr.rounds_dev(dev, chal, rnd).hex() == g["proof"], (opt, val)
+    assert pr.rounds_dev(odd, chal, rnd).hex() == g["proof"], "q_m at an odd address"
     pr.preprocess(dev)
     for opt, val in _SWEEP:
         with hip.options(**{opt: val}):
             assert pr.rounds_dev(dev, chal, rnd, preprocessed=True).hex() == g["proof"], (opt, val, "pre")
+    pr.preprocess(odd)
+    assert pr.rounds_dev(odd, chal, rnd, preprocessed=True).hex() == g["proof"], "q_m at an odd address, pre"

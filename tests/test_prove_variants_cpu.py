@@ -51,9 +51,6 @@ def test_every_variant_both_ways():
     assert V.variants(1008, V.only(V.S1)) == dict(prep=False, numdiv=True, fuse5=False, agg=False)
     assert V.variants(1008, V.only(V.L1)) == dict(prep=True, numdiv=True, fuse5=True, agg=True)
     assert V.vec_modes(1008, V.only(V.L1))[V.L1] == 0 and V.vec_modes(1000, V.ALIGNED)[V.L1] == 1
-    # the options move agg alone
-    assert V.variants(1008, V.ALIGNED, dict(PROVE_EVAL_AGG=0))["agg"] is False
-    assert V.variants(1008, V.ALIGNED, dict(PROVE_FUSE_DIV=1))["agg"] is False
 
 
 def test_launch_model():
@@ -74,9 +71,6 @@ def test_launch_model():
     assert V.launch_delta(1008, V.only(V.FA)) == 1 + 4 + 3 + 1 + 1 - 1
     assert V.launch_delta(1008, V.only(V.ACC)) == 1 + 4 + 1 + 1 + 1 - 1
     assert V.launch_delta(1008, V.only(V.QM)) == 3 and V.launch_delta(1000, V.only(V.QM)) == 1
-    # the two-launch scan is the aligned form too without the aggregates
-    assert V.launch_delta(1008, V.only(V.QM), dict(PROVE_EVAL_AGG=0)) == 2
-    assert V.launch_delta(1008, V.only(V.QM), dict(PROVE_FUSE_DIV=1)) == 3
     deltas = {V.launch_delta(n, res) for n, _, res in _all_cases()}
     assert len(deltas) >= 8, deltas
 

@@ -166,8 +166,8 @@ def test_strict_q_c_in_place(hip, oracle, n):
 @pytest.mark.parametrize("n", V.OPTION_SIZES)
 def test_options_at_placements(hip, oracle, n):
     """List (b) and the q_c-only, q_m-only and s_sigma_1-only placements under the option
-    combinations of test_round5_divisions_vs_oracle (PROVE_FUSE_DIV / PROVE_EVAL_AGG /
-    PROVE_EARLY_COMMITS), test_commitments_srs_log_form (PROVE_SRS_LOGS / PROVE_PACK_FUSE /
+    values of test_round5_divisions_vs_oracle (PROVE_EARLY_COMMITS), the combinations of
+    test_commitments_srs_log_form (PROVE_SRS_LOGS / PROVE_PACK_FUSE /
     PROVE_EARLY_COMMITS) and test_derive_t2a_modes_vs_oracle: the oracle's bytes, and the launch
     difference from the aligned placement under the same options."""
     c = _case(oracle, n)
