@@ -36,6 +36,8 @@
 #include <vector>
 
 #include "plk_device.h"
+#include "plk_hf17.h"
+#include "plk_hostcall.h"
 #include "plk_internal.h"
 
 namespace {
@@ -45,7 +47,8 @@ constexpr int DS_E_LOG = 5, DS_B_LOG = 13;
 constexpr int DS_LEVELS = 8;       // scan levels over DS_T items
 constexpr int DS_JOBS = PLK_DIV_SHORT_LAUNCH_JOBS;
 constexpr int DS_MAX_GRID = 1024;  // blocks per job of the aggregate and apply launches (chunks beyond: grid stride)
-constexpr uint32_t HFP = 17;
+constexpr uint32_t HFP = hf17::P;
+using hf17::mod17;
 static_assert((1 << DS_E_LOG) == DS_E && (1 << DS_B_LOG) == DS_B && (1 << DS_LEVELS) == DS_T, "geometry");
 
 struct DsJob {
@@ -64,9 +67,6 @@ struct DsBatch {
 };
 static_assert(sizeof(DsJob) == 80, "launch structure layout");
 static_assert(sizeof(DsBatch) <= 3072, "the launch structure travels by value: kernel arguments are 4 KiB at most");
-
-// x mod 17 for x < 69632 by a 24-bit multiply: 61681 = (2^20 + 1) / 17
-__device__ __forceinline__ uint32_t mod17(uint32_t x) { return x - 17u * (__umul24(x, 61681u) >> 20); }
 
 template <int T>
 struct Words {
@@ -505,35 +505,6 @@ int launch_jobs(const plk_divshort_job_t* jobs, int n, uint32_t* d_lens, void* d
   return PLK_OK;
 }
 
-// _dev form: the library initialised (PLK_ERR_NODEV without a GPU) and the calling thread on its device
-// (PLK_ERR_ARG otherwise).  The kernels read no library table: nothing is held.
-int use_device(void) {
-  const int rc = plk_ctx_retain();
-  if (rc) return rc;
-  plk_ctx_release();
-  return PLK_OK;
-}
-
-// host form: initialise if need be and make the library's primary device the calling thread's
-int select_device(void) {
-  int rc = plk_init(-1), dev = 0;
-  if (rc) return rc;
-  if (plk_devices(&dev, 1) < 1) {
-    plk_set_error("libplonkhip was shut down during the call");
-    return PLK_ERR_HIP;
-  }
-  PLK_HIP(hipSetDevice(dev));
-  return PLK_OK;
-}
-
-struct Scratch {
-  uint8_t* d = nullptr;
-  ~Scratch() {
-    if (d) (void)hipFree(d);
-  }
-};
-
-size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
 size_t quot_bytes(const plk_divshort_job_t& j) { return j.nl >= j.dl ? j.nl - j.dl + 1 : 1; }
 size_t rem_bytes(const plk_divshort_job_t& j) { return std::min(j.dl - 1, j.nl); }
 
@@ -573,7 +544,7 @@ int plk_poly_divide_short_batch_dev(const plk_divshort_job_t* jobs, int n, uint3
     plk_set_error("%s: d_lens and d_work are required", fn);
     return PLK_ERR_ARG;
   }
-  if ((rc = use_device())) return rc;
+  if ((rc = plk_use_device())) return rc;
   return launch_jobs(jobs, n, d_lens, d_work, (hipStream_t)stream);
 }
 
@@ -585,28 +556,24 @@ int plk_poly_divide_short_batch(const plk_divshort_job_t* jobs, int n, size_t* q
     plk_set_error("%s: quot_lens and rem_lens are required", fn);
     return PLK_ERR_ARG;
   }
-  if ((rc = select_device())) return rc;
+  if ((rc = plk_select_device())) return rc;
   // one allocation: the length words, every job's numerator, quotient and remainder in 16-byte aligned
   // slots, the workspace
   std::vector<plk_divshort_job_t> dj(jobs, jobs + n);
   std::vector<size_t> o_num((size_t)n), o_q((size_t)n), o_r((size_t)n);
-  size_t total = pad16((size_t)3 * n * sizeof(uint32_t));
+  size_t total = plk_pad16((size_t)3 * n * sizeof(uint32_t));
   for (int b = 0; b < n; b++) {
     o_num[b] = total;
-    total += pad16(jobs[b].nl);
+    total += plk_pad16(jobs[b].nl);
     o_q[b] = total;
-    total += pad16(quot_bytes(jobs[b]));
+    total += plk_pad16(quot_bytes(jobs[b]));
     o_r[b] = total;
-    total += pad16(rem_bytes(jobs[b]));
+    total += plk_pad16(rem_bytes(jobs[b]));
   }
   const size_t o_work = total;
   total += work_bytes(jobs, n);
-  Scratch S;
-  if (hipMalloc((void**)&S.d, total) != hipSuccess) {
-    S.d = nullptr;
-    plk_set_error("%s: hipMalloc(%zu) failed", fn, total);
-    return PLK_ERR_NOMEM;
-  }
+  PlkScratch S;
+  if ((rc = S.alloc(fn, total))) return rc;
   for (int b = 0; b < n; b++) {
     PLK_HIP(hipMemcpy(S.d + o_num[b], jobs[b].num, jobs[b].nl, hipMemcpyHostToDevice));
     dj[b].num = S.d + o_num[b];

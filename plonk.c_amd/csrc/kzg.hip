@@ -30,6 +30,8 @@
 #include <vector>
 
 #include "plk_device.h"
+#include "plk_hf17.h"
+#include "plk_hostcall.h"
 #include "plk_internal.h"
 #include "plk_msm_finish.h"
 
@@ -48,7 +50,12 @@ namespace {
 
 constexpr int KZG_T = 256, KZG_E = 16, KZG_CHUNK = KZG_T * KZG_E;
 constexpr int KZG_JOBS = 32;          // jobs per launch
-constexpr uint32_t HFP = 17;
+constexpr uint32_t HFP = hf17::P;
+using hf17::any_noncanonical;
+using hf17::byte_of;
+using hf17::load16;
+using hf17::mod17;
+using hf17::wave_suffix;
 constexpr uint64_t KZG_MAX_LEN = (8ull * 65535ull) * KZG_CHUNK;   // the finish's ticket field: blocks per record
 
 struct KzgJob {
@@ -64,31 +71,6 @@ struct KzgBatch {
   KzgJob j[KZG_JOBS];
 };
 
-// x mod 17 for x < 69632 by a 24-bit multiply: 61681 = (2^20 + 1) / 17
-__device__ __forceinline__ uint32_t mod17(uint32_t x) { return x - 17u * (__umul24(x, 61681u) >> 20); }
-
-// bytes [i, i + 16) of p[0, len) as four words, zero past len; vec: p 16-byte aligned (i is)
-__device__ __forceinline__ void kzg_load16(const uint8_t* p, uint64_t len, uint64_t i, bool vec, uint32_t (&w)[4]) {
-  if (vec && i + 16 <= len) {
-    const uint4 v = *reinterpret_cast<const uint4*>(p + i);
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    return;
-  }
-  w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-  for (int k = 0; k < 16; k++)
-    if (i + k < len) w[k >> 2] |= (uint32_t)p[i + k] << (8 * (k & 3));
-}
-__device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[4], int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xFFu; }
-// some byte of the four words is >= 17, four bytes at a time (additions and masks only: no products).
-// A byte b < 128 has b + 0x6F >= 0x80 exactly when b >= 17, without a carry into the next byte; a
-// byte >= 128 keeps its own top bit.
-__device__ __forceinline__ bool any_noncanonical(const uint32_t (&w)[4]) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) m |= ((w[i] & 0x7F7F7F7Fu) + 0x6F6F6F6Fu) | w[i];
-  return (m & 0x80808080u) != 0;
-}
 // sum_k byte k of w x z^k over the 16 bytes (<= 16 x 255 x 16): the powers packed four to a word
 // (uniform), four v_dot4_u32_u8 on genuine bytes
 __device__ __forceinline__ uint32_t dot_powers(const uint32_t (&w)[4], const uint32_t (&pw)[16]) {
@@ -98,17 +80,6 @@ __device__ __forceinline__ uint32_t dot_powers(const uint32_t (&w)[4], const uin
     t = __builtin_amdgcn_udot4(w[i], pw[4 * i] | pw[4 * i + 1] << 8 | pw[4 * i + 2] << 16 | pw[4 * i + 3] << 24, t, false);
   return t;
 }
-// inclusive suffix sum over the wave: lane l gets the sum over lanes l .. 63
-__device__ __forceinline__ uint32_t wave_suffix(uint32_t x) {
-  const int lane = (int)(threadIdx.x & (PLK_WAVE - 1));
-#pragma unroll
-  for (int d = 1; d < PLK_WAVE; d <<= 1) {
-    const uint32_t v = __shfl_down(x, d, PLK_WAVE);
-    if (lane + d < PLK_WAVE) x += v;
-  }
-  return x;
-}
-
 // Aggregates of job blockIdx.y: one wave per chunk (four 16-byte groups per lane, no LDS, no
 // barrier), chunk 0 skipped -- its aggregate is never read.  One word per chunk:
 // [7:0] sum_i p[i] z^(i mod 16) mod 17 over the chunk, bit 8 set when a byte is >= 17.
@@ -126,7 +97,7 @@ __global__ __launch_bounds__(KZG_T) void kzg_agg_kernel(KzgBatch B, uint32_t* __
   uint32_t w[G][4];
 #pragma unroll
   for (int i = 0; i < G; i++)
-    kzg_load16(J.p, J.len, (uint64_t)c * KZG_CHUNK + (uint64_t)(i * PLK_WAVE + lane) * KZG_E, J.vec & 1u, w[i]);
+    load16(J.p, J.len, (uint64_t)c * KZG_CHUNK + (uint64_t)(i * PLK_WAVE + lane) * KZG_E, J.vec & 1u, w[i]);
   uint32_t acc = 0;
   bool bad = false;
 #pragma unroll
@@ -163,7 +134,7 @@ __global__ __launch_bounds__(KZG_T) void kzg_open_kernel(KzgBatch B, const uint8
   // the thread's 16 consecutive coefficients [base, base + 16), base = 0 mod 16
   const uint64_t base = (uint64_t)c * KZG_CHUNK + (uint64_t)threadIdx.x * KZG_E;
   uint32_t nb[4];
-  kzg_load16(p, len, base, J.vec & 1u, nb);
+  load16(p, len, base, J.vec & 1u, nb);
   uint4 lg = make_uint4(0, 0, 0, 0);
   if (!srs_bad && base < ql) lg = *reinterpret_cast<const uint4*>(logs + base);   // (logs: zero padded to 16)
   bool bad = any_noncanonical(nb) || srs_bad;
@@ -244,7 +215,7 @@ __global__ __launch_bounds__(KZG_T) void kzg_commit_kernel(KzgBatch B, const uin
   if (threadIdx.x < PLK_GROUP_ORDER) etab[threadIdx.x] = exp_words[threadIdx.x];
   const uint64_t base = (uint64_t)c * KZG_CHUNK + (uint64_t)threadIdx.x * KZG_E;
   uint32_t sc[4];
-  kzg_load16(J.p, J.len, base, J.vec & 1u, sc);
+  load16(J.p, J.len, base, J.vec & 1u, sc);
   uint4 lg = make_uint4(0, 0, 0, 0);
   if (!srs_bad && base < J.len) lg = *reinterpret_cast<const uint4*>(logs + base);   // (logs: zero padded to 16)
   uint32_t t = __builtin_amdgcn_udot4(lg.x, sc[0], 0u, false);   // 16 x 101 x 255 < 2^19
@@ -311,7 +282,7 @@ __device__ __forceinline__ void fold_load(const FoldBatch& B, const FoldGroup& G
     }
   } else {
     // byte-wise, as a rolled loop that shifts each byte in from the top (no indexed registers), which
-    // keeps this rare path's code a fraction of the unrolled kzg_load16's
+    // keeps this rare path's code a fraction of the unrolled load16's
 #pragma unroll
     for (int u = 0; u < NB; u++) {
       const FoldPoly& P = B.p[G.first + min(i0 + u, G.k - 1)];
@@ -514,7 +485,6 @@ __global__ __launch_bounds__(KZG_T) void kzg_fold_open_kernel(FoldBatch B, const
 }
 
 uint64_t chunks_of(uint64_t len) { return (len + KZG_CHUNK - 1) / KZG_CHUNK; }
-size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // argument checks shared by the four batch entry points (no device is touched)
 int check_batch(const char* fn, const plk_srs* s, const void* polys, const size_t* lens, const uint8_t* zs, bool open,
@@ -602,22 +572,6 @@ int launch_batch(const plk_srs* s, const uint8_t* const* d_polys, const size_t* 
   return PLK_OK;
 }
 
-// device scratch of one host-buffer call, released on scope exit
-struct Scratch {
-  uint8_t* d = nullptr;
-  ~Scratch() {
-    if (d) (void)hipFree(d);
-  }
-  int alloc(size_t bytes) {
-    if (hipMalloc((void**)&d, bytes) != hipSuccess) {
-      d = nullptr;
-      plk_set_error("plk_kzg: hipMalloc(%zu) failed", bytes);
-      return PLK_ERR_NOMEM;
-    }
-    return PLK_OK;
-  }
-};
-
 // out3 = the reference's fold of sc[0, n) over the first n points of the G1 form (what plk_msm_g1
 // computes): the dlog launch, then the raw serial fold when its record says irregular.
 // d_sc: n scalars on the device; d_res: a zeroed record.
@@ -649,12 +603,12 @@ int host_batch(const plk_srs* s, const uint8_t* const* polys, const size_t* lens
       return PLK_ERR_ARG;
     }
     maxlen = std::max(maxlen, lens[b]);
-    poly_bytes += pad16(lens[b]);
+    poly_bytes += plk_pad16(lens[b]);
   }
-  const size_t o_res = pad16(poly_bytes), o_ys = o_res + (size_t)n * sizeof(PlkMsmResult), o_work = pad16(o_ys + n),
-               o_q = o_work + plk_kzg_workspace(lens, n), total = o_q + pad16(maxlen) + 16;
-  Scratch S;
-  int rc = S.alloc(total);
+  const size_t o_res = plk_pad16(poly_bytes), o_ys = o_res + (size_t)n * sizeof(PlkMsmResult), o_work = plk_pad16(o_ys + n),
+               o_q = o_work + plk_kzg_workspace(lens, n), total = o_q + plk_pad16(maxlen) + 16;
+  PlkScratch S;
+  int rc = S.alloc("plk_kzg", total);
   if (rc) return rc;
   PlkMsmResult* d_res = (PlkMsmResult*)(S.d + o_res);
   PLK_HIP(hipMemsetAsync(d_res, 0, (size_t)n * sizeof(PlkMsmResult), s->st));
@@ -665,7 +619,7 @@ int host_batch(const plk_srs* s, const uint8_t* const* polys, const size_t* lens
     for (int b = 0; b < n; b++) {
       dp[b] = S.d + off;
       PLK_HIP(hipMemcpyAsync(S.d + off, polys[b], lens[b], hipMemcpyHostToDevice, s->st));
-      off += pad16(lens[b]);
+      off += plk_pad16(lens[b]);
     }
     if ((rc = launch_batch(s, dp.data(), lens, zs, n, S.d + o_ys, d_res, nullptr, (uint32_t*)(S.d + o_work), s->st)))
       return rc;
@@ -841,14 +795,14 @@ int host_fold(const plk_srs* s, const uint8_t* const* polys, const size_t* lens,
       return PLK_ERR_ARG;
     }
     maxlen = std::max(maxlen, lens[i]);
-    poly_bytes += pad16(lens[i]);
+    poly_bytes += plk_pad16(lens[i]);
   }
   // records: one per group and a spare for the one-group launches; ys: np and 16 spare
-  const size_t o_res = pad16(poly_bytes), o_ys = o_res + (size_t)(ngroups + 1) * sizeof(PlkMsmResult),
-               o_work = pad16(o_ys + np + PLK_KZG_FOLD_MAX), o_q = o_work + plk_kzg_fold_workspace(lens, start, ngroups),
-               total = o_q + pad16(maxlen) + 16;
-  Scratch S;
-  int rc = S.alloc(total);
+  const size_t o_res = plk_pad16(poly_bytes), o_ys = o_res + (size_t)(ngroups + 1) * sizeof(PlkMsmResult),
+               o_work = plk_pad16(o_ys + np + PLK_KZG_FOLD_MAX), o_q = o_work + plk_kzg_fold_workspace(lens, start, ngroups),
+               total = o_q + plk_pad16(maxlen) + 16;
+  PlkScratch S;
+  int rc = S.alloc("plk_kzg", total);
   if (rc) return rc;
   PlkMsmResult* d_res = (PlkMsmResult*)(S.d + o_res);
   uint32_t* d_work = (uint32_t*)(S.d + o_work);
@@ -858,7 +812,7 @@ int host_fold(const plk_srs* s, const uint8_t* const* polys, const size_t* lens,
   for (int i = 0; i < np; i++) {
     dp[i] = S.d + off;
     PLK_HIP(hipMemcpyAsync(S.d + off, polys[i], lens[i], hipMemcpyHostToDevice, s->st));
-    off += pad16(lens[i]);
+    off += plk_pad16(lens[i]);
   }
   std::vector<uint32_t> irr(ngroups, 1u);
   if (!s->irregular) {
@@ -915,7 +869,7 @@ int plk_srs_create(const uint8_t* g1s, size_t len, plk_srs_t** out) {
   s->dev = plk_cur_device();
   s->len = len;
   s->exp_words = plk_msm_exp_words_dev();
-  const size_t lb = pad16(len) + 16;
+  const size_t lb = plk_pad16(len) + 16;
   rc = s->exp_words ? PLK_OK : PLK_ERR_HIP;
   if (!rc && (hipMalloc((void**)&s->d_g1, 3 * len + 16) != hipSuccess || hipMalloc((void**)&s->d_log, lb) != hipSuccess ||
               hipMalloc((void**)&s->d_flag, 16) != hipSuccess)) {

@@ -35,6 +35,8 @@
 #include <vector>
 
 #include "plk_device.h"
+#include "plk_hf17.h"
+#include "plk_hostcall.h"
 #include "plk_internal.h"
 
 namespace {
@@ -42,7 +44,12 @@ namespace {
 constexpr int LC_T = 256, LC_E = 16, LC_CHUNK = LC_T * LC_E;
 constexpr int LC_JOBS = 24;    // jobs per launch
 constexpr int LC_TERMS = 48;   // terms per launch (>= PLK_LC_MAX_TERMS: any job fits)
-constexpr uint32_t HFP = 17;
+constexpr uint32_t HFP = hf17::P;
+using hf17::add8;
+using hf17::any_noncanonical;
+using hf17::mod17;
+using hf17::neg8;
+using hf17::sub8_wide;
 static_assert(LC_TERMS >= PLK_LC_MAX_TERMS, "a job is never split across launches");
 
 constexpr uint32_t CFG_SUB = 1u << 16, CFG_NEG = 1u << 17, CFG_PASS = 1u << 18;
@@ -71,30 +78,6 @@ struct LcBatch {
 };
 static_assert(sizeof(LcTerm) == 40 && sizeof(LcJob) == 32, "launch structure layout");
 static_assert(sizeof(LcBatch) <= 3072, "the launch structure travels by value: kernel arguments are 4 KiB at most");
-
-// x mod 17 for x < 69632 by a 24-bit multiply: 61681 = (2^20 + 1) / 17
-__device__ __forceinline__ uint32_t mod17(uint32_t x) { return x - 17u * (__umul24(x, 61681u) >> 20); }
-
-// some byte of the four words is >= 17 (kzg.hip any_noncanonical: additions and masks only)
-__device__ __forceinline__ bool any_noncanonical(const uint32_t (&w)[4]) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) m |= ((w[i] & 0x7F7F7F7Fu) + 0x6F6F6F6Fu) | w[i];
-  return (m & 0x80808080u) != 0;
-}
-
-// the reference's byte formulas (src/hf.h:79-119)
-__device__ __forceinline__ uint32_t hf_add8(uint32_t a, uint32_t b) {
-  uint32_t s = (a + b) & 0xFFu;
-  if (s >= HFP) s -= HFP;
-  return s;
-}
-__device__ __forceinline__ uint32_t hf_sub8(uint32_t a, uint32_t b) {
-  int d = (int)(int8_t)((int)(int8_t)a - (int)(int8_t)b);
-  if (d < 0) d = (int)(int8_t)(d + (int)HFP);
-  return (uint32_t)d & 0xFFu;
-}
-__device__ __forceinline__ uint32_t hf_neg8(uint32_t a) { return a == 0 ? 0u : (HFP - a) & 0xFFu; }
 
 // Bytes [i0, i0 + 16) of p[0, len) as four words, zero outside the array (i0 may be negative).
 __device__ __forceinline__ void lc_load16(const uint8_t* p, int64_t len, int64_t i0, uint32_t (&w)[4]) {
@@ -155,11 +138,11 @@ __device__ __forceinline__ uint32_t lc_slow_byte(const LcBatch& B, const LcJob& 
         v = v * pw % HFP;
       }
       if (scale != PLK_LC_RAW) v = v * scale % HFP;
-      if (T.cfg & CFG_NEG) v = hf_neg8(v);
+      if (T.cfg & CFG_NEG) v = neg8(v);
     }
-    acc = t == 0 ? v : (T.cfg & CFG_SUB) ? hf_sub8(acc, v) : hf_add8(acc, v);
+    acc = t == 0 ? v : (T.cfg & CFG_SUB) ? sub8_wide(acc, v) : add8(acc, v);
   }
-  if (j == 0 && J.add_hf >= 0) acc = hf_add8(acc, (uint32_t)J.add_hf);
+  if (j == 0 && J.add_hf >= 0) acc = add8(acc, (uint32_t)J.add_hf);
   return acc;
 }
 
@@ -387,36 +370,6 @@ int launch_jobs(const plk_lc_job_t* jobs, int n, uint32_t* d_nz, hipStream_t st)
   return PLK_OK;
 }
 
-// _dev form: the library initialised (PLK_ERR_NODEV without a GPU) and the calling thread on its device
-// (PLK_ERR_ARG otherwise).  The kernel reads no library table: nothing is held.
-int use_device(void) {
-  const int rc = plk_ctx_retain();
-  if (rc) return rc;
-  plk_ctx_release();
-  return PLK_OK;
-}
-
-// host form: initialise if need be and make the library's primary device the calling thread's
-int select_device(void) {
-  int rc = plk_init(-1), dev = 0;
-  if (rc) return rc;
-  if (plk_devices(&dev, 1) < 1) {
-    plk_set_error("libplonkhip was shut down during the call");
-    return PLK_ERR_HIP;
-  }
-  PLK_HIP(hipSetDevice(dev));
-  return PLK_OK;
-}
-
-struct Scratch {
-  uint8_t* d = nullptr;
-  ~Scratch() {
-    if (d) (void)hipFree(d);
-  }
-};
-
-size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 }  // namespace
 
 extern "C" {
@@ -428,7 +381,7 @@ size_t plk_poly_lincomb_len(const plk_lc_job_t* job) {
 
 int plk_poly_lincomb_batch_dev(const plk_lc_job_t* jobs, int n, uint32_t* d_nz, void* stream) {
   int rc = check_jobs("plk_poly_lincomb_batch_dev", jobs, n);
-  if (rc || (rc = use_device())) return rc;
+  if (rc || (rc = plk_use_device())) return rc;
   return launch_jobs(jobs, n, d_nz, (hipStream_t)stream);
 }
 
@@ -439,26 +392,22 @@ int plk_poly_lincomb(const plk_lc_job_t* job, size_t* out_len) {
     return PLK_ERR_ARG;
   }
   int rc = check_jobs(fn, job, 1);
-  if (rc || (rc = select_device())) return rc;
+  if (rc || (rc = plk_select_device())) return rc;
   // every term uploaded to its own 16-byte aligned slot, the result into one more (out may be a term's p)
   const size_t L = job_len(job);
   size_t total = 16;
-  for (int i = 0; i < job->nterms; i++) total += pad16(job->terms[i].len);
+  for (int i = 0; i < job->nterms; i++) total += plk_pad16(job->terms[i].len);
   const size_t o_out = total;
-  total += pad16(L);
-  Scratch S;
-  if (hipMalloc((void**)&S.d, total) != hipSuccess) {
-    S.d = nullptr;
-    plk_set_error("%s: hipMalloc(%zu) failed", fn, total);
-    return PLK_ERR_NOMEM;
-  }
+  total += plk_pad16(L);
+  PlkScratch S;
+  if ((rc = S.alloc(fn, total))) return rc;
   plk_lc_term_t terms[PLK_LC_MAX_TERMS];
   size_t off = 16;
   for (int i = 0; i < job->nterms; i++) {
     terms[i] = job->terms[i];
     terms[i].p = S.d + off;
     PLK_HIP(hipMemcpy(S.d + off, job->terms[i].p, terms[i].len, hipMemcpyHostToDevice));
-    off += pad16(terms[i].len);
+    off += plk_pad16(terms[i].len);
   }
   plk_lc_job_t dj = *job;
   dj.terms = terms;

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "plk_device.h"
+#include "plk_hostcall.h"
 #include "plk_internal.h"
 
 namespace {
@@ -321,44 +322,6 @@ int launch_runs(const plk_mulshort_run_t* runs, int n, uint32_t* d_nz, hipStream
   return PLK_OK;
 }
 
-// _dev form: the library initialised (PLK_ERR_NODEV without a GPU) and the calling thread on its device
-// (PLK_ERR_ARG otherwise).  The kernel reads no library table: nothing is held.
-int use_device(void) {
-  const int rc = plk_ctx_retain();
-  if (rc) return rc;
-  plk_ctx_release();
-  return PLK_OK;
-}
-
-// host form: initialise if need be and make the library's primary device the calling thread's
-int select_device(void) {
-  int rc = plk_init(-1), dev = 0;
-  if (rc) return rc;
-  if (plk_devices(&dev, 1) < 1) {
-    plk_set_error("libplonkhip was shut down during the call");
-    return PLK_ERR_HIP;
-  }
-  PLK_HIP(hipSetDevice(dev));
-  return PLK_OK;
-}
-
-struct Scratch {
-  uint8_t* d = nullptr;
-  ~Scratch() {
-    if (d) (void)hipFree(d);
-  }
-};
-
-size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-// bytes from the first operand's first byte to the last operand's last; false when that overflows
-bool span_of(size_t len, size_t stride, size_t count, size_t* out) {
-  size_t s = 0;
-  if (__builtin_mul_overflow(count - 1, stride, &s) || __builtin_add_overflow(s, len, &s)) return false;
-  *out = s;
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -381,7 +344,7 @@ int plk_poly_mul_short_plan(size_t la, size_t lb, size_t count, int64_t out[4]) 
 
 int plk_poly_mul_short_batch_dev(const plk_mulshort_run_t* runs, int n, uint32_t* d_nz, void* stream) {
   int rc = check_runs("plk_poly_mul_short_batch_dev", runs, n);
-  if (rc || (rc = use_device())) return rc;
+  if (rc || (rc = plk_use_device())) return rc;
   return launch_runs(runs, n, d_nz, (hipStream_t)stream);
 }
 
@@ -394,29 +357,25 @@ int plk_poly_mul_short_batch(const plk_mulshort_run_t* runs, int n, size_t* out_
   std::vector<size_t> o_a((size_t)n), o_b((size_t)n), o_out((size_t)n), sa((size_t)n), sb((size_t)n);
   size_t products = 0;
   for (int r = 0; r < n; r++) products += runs[r].count;
-  size_t total = pad16(products * sizeof(uint32_t));
+  size_t total = plk_pad16(products * sizeof(uint32_t));
   for (int r = 0; r < n; r++) {
     const plk_mulshort_run_t& S = runs[r];
     size_t so = 0;
-    if (!span_of(S.la, S.a_stride, S.count, &sa[r]) || !span_of(S.lb, S.b_stride, S.count, &sb[r]) ||
-        !span_of(S.la + S.lb - 1, S.la + S.lb - 1, S.count, &so)) {
+    if (!plk_span_of(S.la, S.a_stride, S.count, &sa[r]) || !plk_span_of(S.lb, S.b_stride, S.count, &sb[r]) ||
+        !plk_span_of(S.la + S.lb - 1, S.la + S.lb - 1, S.count, &so)) {
       plk_set_error("%s: run %d: the strides overflow the address space", fn, r);
       return PLK_ERR_RANGE;
     }
     o_a[r] = total;
-    total += pad16(sa[r]);
+    total += plk_pad16(sa[r]);
     o_b[r] = total;
-    total += pad16(sb[r]);
+    total += plk_pad16(sb[r]);
     o_out[r] = total;
-    total += pad16(so);
+    total += plk_pad16(so);
   }
-  if ((rc = select_device())) return rc;
-  Scratch S;
-  if (hipMalloc((void**)&S.d, total) != hipSuccess) {
-    S.d = nullptr;
-    plk_set_error("%s: hipMalloc(%zu) failed", fn, total);
-    return PLK_ERR_NOMEM;
-  }
+  if ((rc = plk_select_device())) return rc;
+  PlkScratch S;
+  if ((rc = S.alloc(fn, total))) return rc;
   for (int r = 0; r < n; r++) {
     PLK_HIP(hipMemcpy(S.d + o_a[r], runs[r].a, sa[r], hipMemcpyHostToDevice));
     PLK_HIP(hipMemcpy(S.d + o_b[r], runs[r].b, sb[r], hipMemcpyHostToDevice));

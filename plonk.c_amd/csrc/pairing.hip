@@ -22,11 +22,13 @@
 // computes it itself, one power per thread, which keeps the entry points free of any table upload.
 #include <algorithm>
 
+#include "plk_hf17.h"
+#include "plk_hostcall.h"
 #include "plk_internal.h"
 
 namespace {
 
-constexpr uint32_t GFP = 101, HFP = 17;
+constexpr uint32_t GFP = 101, HFP = hf17::P;
 constexpr int PAIR_T = 256;
 constexpr uint32_t PAIR_MAX_BLOCKS = 2048;   // 8 blocks per CU; larger batches run the grid-stride loop
 constexpr size_t PAIR_MAX_N = (size_t)1 << 30;
@@ -262,46 +264,6 @@ int check_fold_verify(const char* fn, const plk_kzg_vk_t* vk, int k, bool null_a
   return PLK_OK;
 }
 
-// _dev forms: the library initialised (PLK_ERR_NODEV without a GPU) and the calling thread on its
-// device (PLK_ERR_ARG otherwise: the caller's pointers and stream belong to a device).  The retain is
-// only that check -- the kernels read no library table, so nothing needs holding and it is released
-// at once.
-int use_device(void) {
-  const int rc = plk_ctx_retain();
-  if (rc) return rc;
-  plk_ctx_release();
-  return PLK_OK;
-}
-
-// host forms: initialise if need be and make the library's primary device the calling thread's
-// current one, as the other host-buffer entry points do
-int select_device(void) {
-  int rc = plk_init(-1), dev = 0;
-  if (rc) return rc;
-  if (plk_devices(&dev, 1) < 1) {
-    plk_set_error("libplonkhip was shut down during the call");
-    return PLK_ERR_HIP;
-  }
-  PLK_HIP(hipSetDevice(dev));
-  return PLK_OK;
-}
-
-// device scratch of one host-buffer call, released on scope exit
-struct Scratch {
-  uint8_t* d = nullptr;
-  ~Scratch() {
-    if (d) (void)hipFree(d);
-  }
-  int alloc(const char* fn, size_t bytes) {
-    if (hipMalloc((void**)&d, bytes) != hipSuccess) {
-      d = nullptr;
-      plk_set_error("%s: hipMalloc(%zu) failed", fn, bytes);
-      return PLK_ERR_NOMEM;
-    }
-    return PLK_OK;
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -309,7 +271,7 @@ extern "C" {
 int plk_pairing_batch_dev(const uint8_t* d_g1s, const uint8_t* d_g2s, size_t n, uint8_t* d_out_gt, void* stream) {
   const char* fn = "plk_pairing_batch_dev";
   int rc = check_n(fn, !d_g1s || !d_g2s || !d_out_gt, n);
-  if (rc || (rc = check_range(fn, n)) || (rc = use_device())) return rc;
+  if (rc || (rc = check_range(fn, n)) || (rc = plk_use_device())) return rc;
   hipLaunchKernelGGL(pairing_kernel, dim3(blocks_for(n)), dim3(PAIR_T), 0, (hipStream_t)stream, d_g1s, d_g2s, n, d_out_gt);
   PLK_HIP(hipGetLastError());
   return PLK_OK;
@@ -320,7 +282,7 @@ int plk_kzg_verify_batch_dev(const plk_kzg_vk_t* vk, const uint8_t* d_commits3, 
   const char* fn = "plk_kzg_verify_batch_dev";
   VkWords w;
   int rc = check_n(fn, !vk || !d_commits3 || !d_zs || !d_ys || !d_proofs3 || !d_ok, n);
-  if (rc || (rc = check_vk(fn, vk, &w)) || (rc = check_range(fn, n)) || (rc = use_device())) return rc;
+  if (rc || (rc = check_vk(fn, vk, &w)) || (rc = check_range(fn, n)) || (rc = plk_use_device())) return rc;
   hipLaunchKernelGGL(kzg_verify_kernel, dim3(blocks_for(n)), dim3(PAIR_T), 0, (hipStream_t)stream, w, d_commits3, d_zs, d_ys,
                      d_proofs3, n, d_ok);
   PLK_HIP(hipGetLastError());
@@ -330,8 +292,8 @@ int plk_kzg_verify_batch_dev(const plk_kzg_vk_t* vk, const uint8_t* d_commits3, 
 int plk_pairing_batch(const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t* out_gt) {
   const char* fn = "plk_pairing_batch";
   int rc = check_n(fn, !g1s || !g2s || !out_gt, n);
-  if (rc || (rc = check_range(fn, n)) || (rc = select_device())) return rc;
-  Scratch S;
+  if (rc || (rc = check_range(fn, n)) || (rc = plk_select_device())) return rc;
+  PlkScratch S;
   if ((rc = S.alloc(fn, 7 * n))) return rc;
   uint8_t *d_g1 = S.d, *d_g2 = S.d + 3 * n, *d_out = S.d + 5 * n;
   PLK_HIP(hipMemcpy(d_g1, g1s, 3 * n, hipMemcpyHostToDevice));
@@ -346,8 +308,8 @@ int plk_kzg_verify_batch(const plk_kzg_vk_t* vk, const uint8_t* commits3, const 
   const char* fn = "plk_kzg_verify_batch";
   VkWords w;
   int rc = check_n(fn, !vk || !commits3 || !zs || !ys || !proofs3 || !ok, n);
-  if (rc || (rc = check_vk(fn, vk, &w)) || (rc = check_range(fn, n)) || (rc = select_device())) return rc;
-  Scratch S;
+  if (rc || (rc = check_vk(fn, vk, &w)) || (rc = check_range(fn, n)) || (rc = plk_select_device())) return rc;
+  PlkScratch S;
   if ((rc = S.alloc(fn, 9 * n))) return rc;
   uint8_t *d_c = S.d, *d_w = S.d + 3 * n, *d_z = S.d + 6 * n, *d_y = S.d + 7 * n, *d_ok = S.d + 8 * n;
   PLK_HIP(hipMemcpy(d_c, commits3, 3 * n, hipMemcpyHostToDevice));
@@ -365,7 +327,7 @@ int plk_kzg_verify_fold_batch_dev(const plk_kzg_vk_t* vk, int k, const uint8_t* 
   const char* fn = "plk_kzg_verify_fold_batch_dev";
   VkWords w;
   int rc = check_fold_verify(fn, vk, k, !d_commits3 || !d_weights || !d_ys || !d_zs || !d_proofs3 || !d_ok, n, &w);
-  if (rc || (rc = use_device())) return rc;
+  if (rc || (rc = plk_use_device())) return rc;
   hipLaunchKernelGGL(kzg_verify_fold_kernel, dim3(blocks_for(n)), dim3(PAIR_T), 0, (hipStream_t)stream, w, (uint32_t)k,
                      d_commits3, d_weights, d_ys, d_zs, d_proofs3, n, d_ok);
   PLK_HIP(hipGetLastError());
@@ -377,9 +339,9 @@ int plk_kzg_verify_fold_batch(const plk_kzg_vk_t* vk, int k, const uint8_t* comm
   const char* fn = "plk_kzg_verify_fold_batch";
   VkWords w;
   int rc = check_fold_verify(fn, vk, k, !commits3 || !weights || !ys || !zs || !proofs3 || !ok, n, &w);
-  if (rc || (rc = select_device())) return rc;
+  if (rc || (rc = plk_select_device())) return rc;
   const size_t e = n * (size_t)k;   // entries
-  Scratch S;
+  PlkScratch S;
   if ((rc = S.alloc(fn, 5 * e + 5 * n))) return rc;
   uint8_t *d_c = S.d, *d_wt = S.d + 3 * e, *d_y = S.d + 4 * e, *d_w = S.d + 5 * e, *d_z = d_w + 3 * n, *d_ok = d_z + n;
   PLK_HIP(hipMemcpy(d_c, commits3, 3 * e, hipMemcpyHostToDevice));

@@ -11,6 +11,7 @@
 // paths hold on canonical inputs (or, for poly_eval, on inputs where no uint8 sum can wrap);
 // the kernels detect the other inputs and run the reference's loop serially on the device.
 #include "plk_device.h"
+#include "plk_hf17.h"
 #include "plk_internal.h"
 
 #include <stdlib.h>
@@ -18,20 +19,13 @@
 
 namespace {
 
-constexpr uint32_t HP = 17;
+constexpr uint32_t HP = hf17::P;
+using hf17::add8;
+using hf17::mul8;
+using hf17::noncanonical4;
+using hf17::pow16;
+using hf17::sub8;
 __constant__ uint8_t c_hinv17[17] = {0, 1, 9, 6, 13, 7, 3, 5, 15, 2, 12, 14, 10, 4, 11, 8, 16};
-
-// the reference's raw byte ops (src/hf.h:79-116)
-__device__ __forceinline__ uint32_t raw_add(uint32_t a, uint32_t b) {
-  const uint32_t s = (a + b) & 0xFFu;
-  return s >= HP ? s - HP : s;
-}
-__device__ __forceinline__ uint32_t raw_sub(uint32_t a, uint32_t b) {
-  int8_t d = (int8_t)((int)(int8_t)a - (int)(int8_t)b);
-  if (d < 0) d = (int8_t)(d + (int)HP);
-  return (uint8_t)d;
-}
-__device__ __forceinline__ uint32_t raw_mul(uint32_t a, uint32_t b) { return a * b % HP; }
 
 // block-wide sum of per-thread values (every thread calls; result valid in thread 0)
 template <int NT>
@@ -113,10 +107,10 @@ __global__ __launch_bounds__(EVAL_NT) void eval_batch_kernel(EvalJobs J, uint8_t
   uint32_t out = 0;
   if ((tot >> 48) == 0) {
     const uint32_t S = (uint32_t)(tot & 0xFFFFFFFFull) % HP;
-    out = len ? raw_add(S * xm % HP, p[0]) : 0u;
+    out = len ? add8(S * xm % HP, p[0]) : 0u;
   } else {   // the reference's loop, exactly
     const uint32_t xr = J.x[job];
-    for (uint64_t i = len; i-- > 0;) out = raw_add(raw_mul(out, xr), p[i]);
+    for (uint64_t i = len; i-- > 0;) out = add8(mul8(out, xr), p[i]);
   }
   y[job] = (uint8_t)out;
 }
@@ -139,10 +133,10 @@ __device__ void serial_divide(const uint8_t* __restrict__ num, uint64_t nl, cons
   auto den_at = [&](uint64_t i) -> uint32_t { return den ? den[i] : (i == 0 ? d0 : (i == dl - 1 ? lead : 0u)); };
   const uint32_t inv = c_hinv17[den_at(dl - 1)];   // lead < 17 (host-checked)
   for (uint64_t i = nl; i-- > dl - 1;) {
-    const uint32_t c = raw_mul(run[i], inv);
+    const uint32_t c = mul8(run[i], inv);
     q[i - (dl - 1)] = (uint8_t)c;
     // every j, zero divisor bytes included: hf_sub of raw bytes normalises as the reference does
-    for (uint64_t j = 0; j < dl; j++) run[i - j] = (uint8_t)raw_sub(run[i - j], raw_mul(c, den_at(dl - 1 - j)));
+    for (uint64_t j = 0; j < dl; j++) run[i - j] = (uint8_t)sub8(run[i - j], mul8(c, den_at(dl - 1 - j)));
   }
   for (uint64_t i = 0; i < rl; i++) rem[i] = run[i];
 }
@@ -236,12 +230,6 @@ __global__ __launch_bounds__(256) void div_binom_short_kernel(Binom B) {
 // aggregates after it and scans within itself.  A = 0 needs no scan (q = v).
 constexpr int SCAN_T = 256, SCAN_E = 16, SCAN_B = SCAN_T * SCAN_E;
 
-__device__ __forceinline__ void pow16(uint32_t a, uint32_t (&pw)[16]) {
-  pw[0] = 1;
-#pragma unroll
-  for (int j = 1; j < 16; j++) pw[j] = pw[j - 1] * a % HP;
-}
-
 // chain r = blockIdx.y + y0, positions [blockIdx.x SCAN_B, +SCAN_B)
 __global__ __launch_bounds__(SCAN_T) void div_binom_sums_kernel(Binom B, uint64_t y0, uint64_t nblk,
                                                                 uint32_t* __restrict__ bsum) {
@@ -333,7 +321,7 @@ __global__ __launch_bounds__(SCAN_T) void div_binom_apply_kernel(Binom B, uint64
 __global__ __launch_bounds__(256) void div_const_kernel(const uint8_t* __restrict__ num, uint64_t nl, uint32_t inv,
                                                         uint8_t* __restrict__ q) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nl; i += (uint64_t)gridDim.x * blockDim.x)
-    q[i] = (uint8_t)raw_mul(num[i], inv);
+    q[i] = (uint8_t)mul8(num[i], inv);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -347,10 +335,6 @@ __global__ __launch_bounds__(256) void div_const_kernel(const uint8_t* __restric
 struct __attribute__((packed, aligned(1))) U4u {   // 16 bytes at any address (caller buffers)
   uint32_t x, y, z, w;
 };
-// non-zero when some byte of w is >= 17
-__device__ __forceinline__ uint32_t bad4(uint32_t w) {
-  return (((w & 0x7F7F7F7Fu) + 0x6F6F6F6Fu) | w) & 0x80808080u;
-}
 // per byte (17 - b) % 17, bytes < 17
 __device__ __forceinline__ uint32_t neg4(uint32_t w) {
   uint32_t r = 0;
@@ -389,7 +373,7 @@ __global__ __launch_bounds__(256) void div_reverse_kernel(RevJobs J) {
     const uint64_t j0 = c << 4;
     if (j0 + 16 <= jb.n) {
       const U4u v = *reinterpret_cast<const U4u*>(jb.src + (jb.n - 16 - j0));
-      bad |= bad4(v.x) | bad4(v.y) | bad4(v.z) | bad4(v.w);
+      bad |= noncanonical4(v.x) | noncanonical4(v.y) | noncanonical4(v.z) | noncanonical4(v.w);
       U4u o;
       o.x = __builtin_bswap32(v.w);
       o.y = __builtin_bswap32(v.z);
@@ -486,7 +470,7 @@ __global__ __launch_bounds__(256) void div_rem_sub_kernel(const uint8_t* __restr
     if (i0 + 16 <= m) {
       const U4u a = *reinterpret_cast<const U4u*>(num + i0);
       const U4u r = *reinterpret_cast<const U4u*>(R + i0);
-      bad |= bad4(a.x) | bad4(a.y) | bad4(a.z) | bad4(a.w);
+      bad |= noncanonical4(a.x) | noncanonical4(a.y) | noncanonical4(a.z) | noncanonical4(a.w);
       U4u o;
       o.x = sub4(a.x, r.x);
       o.y = sub4(a.y, r.y);
@@ -515,7 +499,7 @@ __global__ void matrix_mul_kernel(const uint8_t* __restrict__ a, const uint8_t* 
   for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m * n; e += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t i = e / n, j = e % n;
     uint32_t s = 0;
-    for (uint64_t t = 0; t < k; t++) s = raw_add(s, raw_mul(a[i * k + t], b[t * n + j]));
+    for (uint64_t t = 0; t < k; t++) s = add8(s, mul8(a[i * k + t], b[t * n + j]));
     out[e] = (uint8_t)s;
   }
 }
@@ -563,7 +547,7 @@ __global__ __launch_bounds__(256) void matrix_inv_kernel(const uint8_t* __restri
     __syncthreads();
     if (div != 0)   // hf_div(value, div) = value * inv(div); div < 17 (host-checked bytes)
       for (uint64_t k = threadIdx.x; k < cols; k += blockDim.x)
-        aug[r * cols + k] = (uint8_t)raw_mul(aug[r * cols + k], c_hinv17[div]);
+        aug[r * cols + k] = (uint8_t)mul8(aug[r * cols + k], c_hinv17[div]);
     __syncthreads();
     // eliminate every other row (src/matrix.h:130-143): rows are independent given row r, so in
     // parallel; each row's multiplier is captured before its update
@@ -573,7 +557,7 @@ __global__ __launch_bounds__(256) void matrix_inv_kernel(const uint8_t* __restri
     for (uint64_t e = threadIdx.x; e < n * cols; e += blockDim.x) {
       const uint64_t ii = e / cols, k = e % cols;
       if (ii == r) continue;
-      aug[e] = (uint8_t)raw_sub(aug[e], raw_mul(aug[r * cols + k], mults[ii]));
+      aug[e] = (uint8_t)sub8(aug[e], mul8(aug[r * cols + k], mults[ii]));
     }
     __syncthreads();
     lead++;

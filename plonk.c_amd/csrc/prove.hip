@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "plk_device.h"
+#include "plk_hf17.h"
 #include "plk_internal.h"
 #include "plk_msm_finish.h"
 
@@ -41,7 +42,11 @@
 
 namespace {
 
-constexpr uint32_t HFP = 17;
+constexpr uint32_t HFP = hf17::P;
+using hf17::load16;
+using hf17::mod17;   // every call site's bound is noted
+using hf17::pow16;
+using hf17::wave_suffix;
 
 // ------------------------------------------------------------------ scalar file layout
 enum Slot : int {
@@ -75,23 +80,6 @@ enum Stat : int {
   NSTAT = 16
 };
 
-__device__ __forceinline__ uint32_t hneg(uint32_t a) { return a ? HFP - a : 0; }
-// x mod 17 for x < 69632 by 24-bit multiplies (full rate; `% 17` on a u32 takes a quarter-rate
-// multiply-high): 61681 = (2^20 + 1) / 17, so floor(x 61681 / 2^20) = floor(x / 17) for x < 2^20,
-// and x 61681 < 2^32 (checked on the host for every x < 69632).  Every call site's bound is noted.
-__device__ __forceinline__ uint32_t hmod(uint32_t x) { return x - 17u * (__umul24(x, 61681u) >> 20); }
-__device__ __forceinline__ uint32_t hpow_d(uint32_t b, uint64_t e) {
-  uint32_t r = 1;
-  b %= HFP;
-  while (e) {
-    if (e & 1) r = r * b % HFP;
-    b = b * b % HFP;
-    e >>= 1;
-  }
-  return r;
-}
-__device__ __forceinline__ uint32_t hinv(uint32_t a) { return hpow_d(a, HFP - 2); }   // inv(0) = 0 (hf.h LUT)
-
 // ------------------------------------------------------------------ lincomb
 // out[i] = S[scale] * (sum_t S[slot_t] * p_t[i] + [i==0] S[c0] + [i==1] S[c1]) mod 17,
 // optionally times S[twist]^i.  Covers poly_add/sub/scale/add_hf chains (src/poly.h:67-104,
@@ -117,9 +105,7 @@ __global__ __launch_bounds__(256) void lincomb_kernel(LcArgs a, const uint8_t* _
   const uint32_t c0 = a.c0 >= 0 ? S[a.c0] : 0u, c1 = a.c1 >= 0 ? S[a.c1] : 0u;
   uint32_t tw[16];
   const uint32_t x = a.twist >= 0 ? S[a.twist] : 1u;
-  tw[0] = 1;
-#pragma unroll
-  for (int j = 1; j < 16; j++) tw[j] = tw[j - 1] * x % HFP;
+  pow16(x, tw);
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.out_len; i += stride) {
     uint32_t acc = i == 0 ? c0 : (i == 1 ? c1 : 0u);
@@ -130,20 +116,6 @@ __global__ __launch_bounds__(256) void lincomb_kernel(LcArgs a, const uint8_t* _
     if (a.twist >= 0) v = v * (i == 0 ? 1u : (x == 0 ? 0u : tw[i & 15])) % HFP;
     a.out[i] = (uint8_t)v;
   }
-}
-
-// 16 coefficients per thread and iteration (uint4 loads / stores); every pointer 16-byte
-// aligned (checked on the host, else lincomb_kernel).
-__device__ __forceinline__ void load16(const uint8_t* p, uint64_t len, uint64_t i, uint32_t (&w)[4]) {
-  if (i + 16 <= len) {
-    const uint4 q = *reinterpret_cast<const uint4*>(p + i);
-    w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-    return;
-  }
-  w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-  for (int k = 0; k < 16; k++)
-    if (i + k < len) w[k >> 2] |= (uint32_t)p[i + k] << (8 * (k & 3));
 }
 
 // p readable in whole 16-byte chunks up to len (16-byte aligned): one unconditional uint4
@@ -158,6 +130,8 @@ __device__ __forceinline__ void load16_masked(const uint8_t* p, uint64_t len, ui
     w[k] = cnt >= 4 ? v[k] : (cnt <= 0 ? 0u : v[k] & ((1u << (8 * cnt)) - 1u));
   }
 }
+// 16 coefficients per thread and iteration (uint4 loads / stores); every pointer 16-byte
+// aligned (checked on the host, else lincomb_kernel): load16's vec is true throughout this file.
 __global__ __launch_bounds__(256) void lincomb16_kernel(LcArgs a, const uint8_t* __restrict__ S) {
   uint32_t cf[LC_MAX];
 #pragma unroll
@@ -166,9 +140,7 @@ __global__ __launch_bounds__(256) void lincomb16_kernel(LcArgs a, const uint8_t*
   const uint32_t c0 = a.c0 >= 0 ? S[a.c0] : 0u, c1 = a.c1 >= 0 ? S[a.c1] : 0u;
   const uint32_t x = a.twist >= 0 ? S[a.twist] : 1u;
   uint32_t tw[16];   // x^k; x^i = 1 for i = 0 mod 16 when x != 0
-  tw[0] = 1;
-#pragma unroll
-  for (int k = 1; k < 16; k++) tw[k] = tw[k - 1] * x % HFP;
+  pow16(x, tw);
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * 16;
   for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16; i < a.out_len; i += stride) {
     uint32_t acc[16];
@@ -179,7 +151,7 @@ __global__ __launch_bounds__(256) void lincomb16_kernel(LcArgs a, const uint8_t*
     for (int t = 0; t < LC_MAX; t++) {
       if (t < a.nt && i < a.len[t]) {
         uint32_t w[4];
-        load16(a.p[t], a.len[t], i, w);
+        load16(a.p[t], a.len[t], i, true, w);
 #pragma unroll
         for (int k = 0; k < 16; k++) acc[k] += cf[t] * ((w[k >> 2] >> (8 * (k & 3))) & 0xFFu);
       }
@@ -187,8 +159,8 @@ __global__ __launch_bounds__(256) void lincomb16_kernel(LcArgs a, const uint8_t*
     uint32_t o[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int k = 0; k < 16; k++) {
-      uint32_t v = hmod(hmod(acc[k]) * sc);   // (acc <= 16 terms x 16 x 255 + 32 < 69632)
-      if (a.twist >= 0) v = hmod(v * (x == 0 ? (i + k == 0 ? 1u : 0u) : tw[k]));
+      uint32_t v = mod17(mod17(acc[k]) * sc);   // (acc <= 16 terms x 16 x 255 + 32 < 69632)
+      if (a.twist >= 0) v = mod17(v * (x == 0 ? (i + k == 0 ? 1u : 0u) : tw[k]));
       o[k >> 2] |= v << (8 * (k & 3));
     }
     if (i + 16 <= a.out_len) {
@@ -263,7 +235,7 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a, const SlotFile f,
     {
       const uint32_t w = load4(a.zh, a.lz, i);
 #pragma unroll
-      for (int k = 0; k < 4; k++) z[k + 2] = hmod((w >> (8 * k)) & 0xFFu);
+      for (int k = 0; k < 4; k++) z[k + 2] = mod17((w >> (8 * k)) & 0xFFu);
       z[0] = (i >= 2 && i - 2 < a.lz) ? a.zh[i - 2] % HFP : 0u;
       z[1] = (i >= 1 && i - 1 < a.lz) ? a.zh[i - 1] % HFP : 0u;
     }
@@ -276,20 +248,20 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a, const SlotFile f,
       const int sh = 8 * k;
       auto byte = [&](uint32_t f) { return (f >> sh) & 0xFFu; };
       const uint32_t c0 = (i + k == 0), c1 = (i + k == 1);
-      // (hmod bounds: scalars < 17, bytes < 256: every argument < 16 (16 + 3 * 256 + 256))
-      const uint32_t va = hmod(ba0 * z[k + 2] + ba1 * z[k + 1] + byte(fa));
-      const uint32_t vb = hmod(bb0 * z[k + 2] + bb1 * z[k + 1] + byte(fb));
-      const uint32_t vc = hmod(bc0 * z[k + 2] + bc1 * z[k + 1] + byte(fc));
-      const uint32_t vz = hmod(bz0 * z[k + 2] + bz1 * z[k + 1] + bz2 * z[k] + byte(fz));
+      // (mod17 bounds: scalars < 17, bytes < 256: every argument < 16 (16 + 3 * 256 + 256))
+      const uint32_t va = mod17(ba0 * z[k + 2] + ba1 * z[k + 1] + byte(fa));
+      const uint32_t vb = mod17(bb0 * z[k + 2] + bb1 * z[k + 1] + byte(fb));
+      const uint32_t vc = mod17(bc0 * z[k + 2] + bc1 * z[k + 1] + byte(fc));
+      const uint32_t vz = mod17(bz0 * z[k + 2] + bz1 * z[k + 1] + bz2 * z[k] + byte(fz));
       oA |= va << sh; oB |= vb << sh; oC |= vc << sh; oZ |= vz << sh;
-      oA2 |= hmod((va + c0 * ga + c1 * be) * al) << sh;
-      oB2 |= hmod(vb + c0 * ga + c1 * bk1) << sh;
-      oC2 |= hmod(vc + c0 * ga + c1 * bk2) << sh;
-      oA3 |= hmod((va + be * byte(f1) + c0 * ga) * al) << sh;
-      oB3 |= hmod(vb + be * byte(f2) + c0 * ga) << sh;
-      oC3 |= hmod(vc + be * byte(f3) + c0 * ga) << sh;
-      oZW |= hmod(vz * (om == 0 ? c0 : tw[k])) << sh;
-      oZ1 |= hmod((vz + c0 * 16u) * al2) << sh;
+      oA2 |= mod17((va + c0 * ga + c1 * be) * al) << sh;
+      oB2 |= mod17(vb + c0 * ga + c1 * bk1) << sh;
+      oC2 |= mod17(vc + c0 * ga + c1 * bk2) << sh;
+      oA3 |= mod17((va + be * byte(f1) + c0 * ga) * al) << sh;
+      oB3 |= mod17(vb + be * byte(f2) + c0 * ga) << sh;
+      oC3 |= mod17(vc + be * byte(f3) + c0 * ga) << sh;
+      oZW |= mod17(vz * (om == 0 ? c0 : tw[k])) << sh;
+      oZ1 |= mod17((vz + c0 * 16u) * al2) << sh;
     }
     store4(a.cA, a.la, i, oA); store4(a.cB, a.la, i, oB); store4(a.cC, a.la, i, oC);
     // (NULL: not needed by this call -- A2 B2 derived from a_x b_x by t2a_kernel, or a chain whose
@@ -336,9 +308,9 @@ __global__ __launch_bounds__(256) void t2a_kernel(const uint8_t* __restrict__ ab
       const uint32_t ak = (wa >> sh) & 0xFFu, bk = (wb >> sh) & 0xFFu;
       const uint32_t am = k ? (wa >> (sh - 8)) & 0xFFu : pa, bm = k ? (wb >> (sh - 8)) & 0xFFu : pb;
       const uint64_t j = i + k;
-      // (hmod bound: 16 + 16 * 32 + 2 * 16 * 16 + 289 < 69632)
+      // (mod17 bound: 16 + 16 * 32 + 2 * 16 * 16 + 289 < 69632)
       const uint32_t v = ((wab >> sh) & 0xFFu) + ga * (ak + bk) + bk1 * am + be * bm + (j < 3 ? K[j] : 0u);
-      o |= hmod(hmod(v) * al) << sh;
+      o |= mod17(mod17(v) * al) << sh;
     }
     store4(out, lab, i, o);
   }
@@ -358,9 +330,7 @@ __global__ __launch_bounds__(256) void lincomb16_batch_kernel(LcBatch b, const u
   const uint32_t c0 = a.c0 >= 0 ? S[a.c0] : 0u, c1 = a.c1 >= 0 ? S[a.c1] : 0u;
   const uint32_t x = a.twist >= 0 ? S[a.twist] : 1u;
   uint32_t tw[16];
-  tw[0] = 1;
-#pragma unroll
-  for (int k = 1; k < 16; k++) tw[k] = tw[k - 1] * x % HFP;
+  pow16(x, tw);
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * 16;
   for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16; i < a.out_len; i += stride) {
     uint32_t acc[16];
@@ -371,7 +341,7 @@ __global__ __launch_bounds__(256) void lincomb16_batch_kernel(LcBatch b, const u
     for (int t = 0; t < LC_MAX; t++) {
       if (t < a.nt && i < a.len[t]) {
         uint32_t w[4];
-        load16(a.p[t], a.len[t], i, w);
+        load16(a.p[t], a.len[t], i, true, w);
 #pragma unroll
         for (int k = 0; k < 16; k++) acc[k] += cf[t] * ((w[k >> 2] >> (8 * (k & 3))) & 0xFFu);
       }
@@ -379,8 +349,8 @@ __global__ __launch_bounds__(256) void lincomb16_batch_kernel(LcBatch b, const u
     uint32_t o[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int k = 0; k < 16; k++) {
-      uint32_t v = hmod(hmod(acc[k]) * sc);   // (acc <= 16 terms x 16 x 255 + 32 < 69632)
-      if (a.twist >= 0) v = hmod(v * (x == 0 ? (i + k == 0 ? 1u : 0u) : tw[k]));
+      uint32_t v = mod17(mod17(acc[k]) * sc);   // (acc <= 16 terms x 16 x 255 + 32 < 69632)
+      if (a.twist >= 0) v = mod17(v * (x == 0 ? (i + k == 0 ? 1u : 0u) : tw[k]));
       o[k >> 2] |= v << (8 * (k & 3));
     }
     if (i + 16 <= a.out_len) {
@@ -462,9 +432,7 @@ __device__ __forceinline__ void eval_row_block(const EvArgs& a, int e, uint32_t 
                                                uint32_t* tick, uint32_t* stat, bool top) {
   const uint32_t x = S[a.xslot[e]];
   uint32_t pw[16];
-  pw[0] = 1;
-#pragma unroll
-  for (int j = 1; j < 16; j++) pw[j] = pw[j - 1] * x % HFP;
+  pow16(x, pw);
   const uint8_t* p = a.p[e];
   const uint64_t n = a.len[e];
   uint32_t acc = 0;
@@ -491,12 +459,12 @@ __device__ __forceinline__ void eval_row_block(const EvArgs& a, int e, uint32_t 
 #pragma unroll
       for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);   // (<= 64 x 16)
       if (lane == 0) {
-        s = hmod(s);
+        s = mod17(s);
         a.agg[16 * ((uint64_t)a.coff[e] + c) + a.col[e]] = (uint8_t)s;
         acc += s;
       }
     }
-    acc = hmod(acc);
+    acc = mod17(acc);
   } else if (a.vec[e] == 2) {         // readable in whole chunks: 4 loads in flight per thread
     for (uint64_t i0 = gid * 16; i0 < n; i0 += 4 * stride) {
       uint32_t w[4][4];
@@ -513,7 +481,7 @@ __device__ __forceinline__ void eval_row_block(const EvArgs& a, int e, uint32_t 
   } else if (a.vec[e]) {              // 16 coefficients per step: i = 0 mod 16 so x^(i+k) = x^k
     for (uint64_t i = gid * 16; i < n; i += stride) {
       uint32_t w[4];
-      load16(p, n, i, w);
+      load16(p, n, i, true, w);
       uint32_t s = 0;
 #pragma unroll
       for (int k = 0; k < 16; k++) s += pw[k] * ((w[k >> 2] >> (8 * (k & 3))) & 0xFFu);
@@ -592,8 +560,8 @@ __global__ __launch_bounds__(256) void divide_binomial_kernel(const uint8_t* __r
                                                               uint32_t* __restrict__ rem_flag) {
   const uint64_t r0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t r = r0 < m ? r0 : m;   // lanes past m idle but stay for the wave vote
-  const uint32_t li = hinv(lead);
-  const uint32_t nc = hneg(c);
+  const uint32_t li = hf17::inv(lead);
+  const uint32_t nc = hf17::neg(c);
   uint32_t prev = 0;   // q[j + m]
   const uint64_t cnt = (r < m && nl > m && r < ql) ? (ql - 1 - r) / m + 1 : 0;   // chain length
   if (cnt <= 8) {
@@ -637,8 +605,8 @@ __global__ __launch_bounds__(256) void divide_binomial4_kernel(const uint8_t* __
                                                                uint8_t* __restrict__ q, uint64_t ql, uint64_t cq,
                                                                uint64_t cr, uint8_t* __restrict__ rem_part) {
   const uint64_t r0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  const uint32_t li = hinv(lead);
-  const uint32_t nc = hneg(c);
+  const uint32_t li = hf17::inv(lead);
+  const uint32_t nc = hf17::neg(c);
   auto chain = [&](uint64_t r) -> uint64_t { return (r < m && nl > m && r < ql) ? (r <= cr ? cq + 1 : cq) : 0; };
   const uint64_t cnt0 = chain(r0);   // the longest of the 4 (chain length falls with r)
   uint32_t rv = 0;
@@ -657,7 +625,7 @@ __global__ __launch_bounds__(256) void divide_binomial4_kernel(const uint8_t* __
 #pragma unroll
         for (int b = 0; b < 4; b++) {
           if ((uint32_t)k >= skip[b]) {
-            const uint32_t v = hmod((((w[k] >> (8 * b)) & 0xFFu) + nc * prev[b]) * li);   // (<= (255 + 256) x 16)
+            const uint32_t v = mod17((((w[k] >> (8 * b)) & 0xFFu) + nc * prev[b]) * li);   // (<= (255 + 256) x 16)
             prev[b] = v;
             o |= v << (8 * b);
           }
@@ -739,7 +707,7 @@ __device__ __forceinline__ uint32_t lc_word(const LcArgs& a, const uint32_t (&cf
   }
   uint32_t o = 0;
 #pragma unroll
-  for (int b = 0; b < 4; b++) o |= hmod(hmod(acc[b]) * sc) << (8 * b);   // (acc <= 8 x 16 x 255 + 16)
+  for (int b = 0; b < 4; b++) o |= mod17(mod17(acc[b]) * sc) << (8 * b);   // (acc <= 8 x 16 x 255 + 16)
   return o;
 }
 template <int NT, int KMAX>
@@ -753,8 +721,8 @@ __global__ __launch_bounds__(256) void numdiv_kernel(LcArgs a, const uint8_t* __
   const uint32_t c0 = a.c0 >= 0 ? S[a.c0] : 0u, c1 = a.c1 >= 0 ? S[a.c1] : 0u;
   const uint64_t nl = a.out_len;
   const uint64_t r0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  const uint32_t li = hinv(lead);
-  const uint32_t nc = hneg(c);
+  const uint32_t li = hf17::inv(lead);
+  const uint32_t nc = hf17::neg(c);
   auto chain = [&](uint64_t r) -> uint64_t { return (r < m && nl > m && r < ql) ? (r <= cr ? cq + 1 : cq) : 0; };
   const uint64_t cnt0 = chain(r0);
   uint32_t w[KMAX];   // chains are at most KMAX = cq + 1 long (host): no branch around the loads
@@ -775,7 +743,7 @@ __global__ __launch_bounds__(256) void numdiv_kernel(LcArgs a, const uint8_t* __
 #pragma unroll
       for (int b = 0; b < 4; b++) {
         if ((uint32_t)k >= skip[b]) {
-          const uint32_t v = hmod((((w[k] >> (8 * b)) & 0xFFu) + nc * prev[b]) * li);   // (<= (255 + 256) x 16)
+          const uint32_t v = mod17((((w[k] >> (8 * b)) & 0xFFu) + nc * prev[b]) * li);   // (<= (255 + 256) x 16)
           prev[b] = v;
           o |= v << (8 * b);
         }
@@ -815,7 +783,7 @@ __global__ __launch_bounds__(256) void numdiv_kernel(LcArgs a, const uint8_t* __
 #pragma unroll
   for (int b = 0; b < 4; b++) {
     const uint64_t r = r0 + b;
-    if (r < m && r < nl && hmod(((wr >> (8 * b)) & 0xFFu) + nc * prev[b])) rv = 1;
+    if (r < m && r < nl && mod17(((wr >> (8 * b)) & 0xFFu) + nc * prev[b])) rv = 1;
   }
   const int vote = __syncthreads_or(rv != 0);
   if (threadIdx.x == 0) rem_part[blockIdx.x] = vote ? 1 : 0;
@@ -844,16 +812,6 @@ struct LinDiv {
 __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-// inclusive suffix sum: lane l gets the sum over lanes l .. 63
-__device__ __forceinline__ uint32_t wave_suffix(uint32_t x) {
-  const int lane = (int)(threadIdx.x & 63);
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t v = __shfl_down(x, d, 64);
-    if (lane + d < 64) x += v;
-  }
   return x;
 }
 // block sum of SCAN_T threads' values (< 2^26 / SCAN_T each) for thread 0: wave sums + one barrier
@@ -929,9 +887,7 @@ __global__ __launch_bounds__(SCAN_T) void lin_scan_sums_kernel(LinDivs L, const 
   const uint64_t nl = D.nl;
   const uint32_t a = S[D.aslot];
   uint32_t pw[16];
-  pw[0] = 1;
-#pragma unroll
-  for (int j = 1; j < 16; j++) pw[j] = pw[j - 1] * a % HFP;
+  pow16(a, pw);
   const uint64_t base = (uint64_t)blockIdx.x * SCAN_B + threadIdx.x;
   uint32_t acc = 0;
 #pragma unroll
@@ -954,15 +910,13 @@ __global__ __launch_bounds__(SCAN_T) void lin_scan_apply_kernel(LinDivs L, const
   uint8_t* q = D.q;
   const uint32_t a = S[D.aslot];
   uint32_t pw[16], ipw[16];
-  pw[0] = ipw[0] = 1;
-  const uint32_t ai = hinv(a);
-#pragma unroll
-  for (int j = 1; j < 16; j++) { pw[j] = pw[j - 1] * a % HFP; ipw[j] = ipw[j - 1] * ai % HFP; }
+  pow16(a, pw);
+  pow16(hf17::inv(a), ipw);
   // thread owns SCAN_E = 16 consecutive elements [base, base + 16): base % 16 = 0
   const uint64_t base = (uint64_t)blockIdx.x * SCAN_B + (uint64_t)threadIdx.x * SCAN_E;
   uint32_t nb8[4] = {0, 0, 0, 0};
   if (D.vec) {
-    load16(num, nl, base, nb8);
+    load16(num, nl, base, true, nb8);
   } else {
 #pragma unroll
     for (int k = 0; k < 16; k++)
@@ -973,7 +927,7 @@ __global__ __launch_bounds__(SCAN_T) void lin_scan_apply_kernel(LinDivs L, const
 #pragma unroll
   for (int k = 0; k < SCAN_E; k++) {
     const uint64_t i = base + k;
-    w[k] = (i > 0) ? hmod(((nb8[k >> 2] >> (8 * (k & 3))) & 0xFFu) * pw[k]) : 0u;   // (<= 255 x 16)
+    w[k] = (i > 0) ? mod17(((nb8[k >> 2] >> (8 * (k & 3))) & 0xFFu) * pw[k]) : 0u;   // (<= 255 x 16)
     tot += w[k];
   }
   uint32_t c = 0;
@@ -1029,7 +983,7 @@ __device__ __forceinline__ void lin_div_finish(const LcArgs& a, const LinDiv& D,
   uint32_t w[E], tot = 0;
 #pragma unroll
   for (int k = 0; k < E; k++) {
-    w[k] = base + k > 0 ? hmod(((nb8[k >> 2] >> (8 * (k & 3))) & 0xFFu) * pt[k]) : 0u;
+    w[k] = base + k > 0 ? mod17(((nb8[k >> 2] >> (8 * (k & 3))) & 0xFFu) * pt[k]) : 0u;
     tot += w[k];
   }
   // a = 0: q[j] = num[j + 1], which for the thread's last coefficient is the next thread's first
@@ -1044,12 +998,12 @@ __device__ __forceinline__ void lin_div_finish(const LcArgs& a, const LinDiv& D,
       const uint64_t i = base + E;
       uint32_t s = 0;
       for (int u = 0; u < a.nt; u++) s += i < a.len[u] ? cf[u] * a.p[u][i] : 0u;
-      first[T / 64] = i < nl ? hmod(hmod(s) * sc) : 0u;
+      first[T / 64] = i < nl ? mod17(mod17(s) * sc) : 0u;
     }
   }
   // suffix sums: lanes, waves, then the later chunks' carry -- one barrier
   const uint32_t suf = wave_suffix(tot);                 // (<= 64 x E x 16)
-  const uint32_t cw = hmod(wave_sum(carry));             // (the wave sum <= 64 x 16)
+  const uint32_t cw = mod17(wave_sum(carry));             // (the wave sum <= 64 x 16)
   __shared__ uint32_t ws[2][T / 64];
   if (lane == 0) {
     ws[0][wv] = suf;
@@ -1060,7 +1014,7 @@ __device__ __forceinline__ void lin_div_finish(const LcArgs& a, const LinDiv& D,
   uint32_t run = suf - tot;
 #pragma unroll
   for (int u = 0; u < T / 64; u++) run += (u > wv ? ws[0][u] : 0u) + ws[1][u];
-  run = hmod(run);   // (<= 4096 x 16 + T / 64 x 16 < 69632)
+  run = mod17(run);   // (<= 4096 x 16 + T / 64 x 16 < 69632)
   const uint64_t ql = nl - 1;
   uint32_t o[E / 4] = {};
 #pragma unroll
@@ -1068,7 +1022,7 @@ __device__ __forceinline__ void lin_div_finish(const LcArgs& a, const LinDiv& D,
     const uint64_t j = base + k;   // run = sum_{i > j} w_i (mod 17: < 17 + (E - 1) x 16 below)
     if (j < ql) {
       const uint32_t nx = k == E - 1 ? nxt : (nb8[(k + 1) >> 2] >> (8 * ((k + 1) & 3))) & 0xFFu;
-      const uint32_t v = av == 0 ? nx : hmod(hmod(run) * ipt[k]);
+      const uint32_t v = av == 0 ? nx : mod17(mod17(run) * ipt[k]);
       o[k >> 2] |= v << (8 * (k & 3));
       if (j == 0 && ((nb8[0] & 0xFFu) + av * v) % HFP) atomicOr(D.flag, 1u);
     }
@@ -1085,12 +1039,10 @@ __device__ __forceinline__ void lin_div_finish(const LcArgs& a, const LinDiv& D,
 }
 // av^k and av^-(k + 1) for k < 16 (exponents mod 16: av^16 = 1 for av != 0)
 __device__ __forceinline__ void div_powers(uint32_t av, uint32_t (&pw)[16], uint32_t (&ipw)[16]) {
-  const uint32_t ai = hinv(av);
-  pw[0] = 1;
+  const uint32_t ai = hf17::inv(av);
+  pow16(av, pw);
   ipw[15] = 1;   // av^-16 = av^0
   uint32_t x = ai;
-#pragma unroll
-  for (int j = 1; j < 16; j++) pw[j] = pw[j - 1] * av % HFP;
 #pragma unroll
   for (int j = 0; j < 15; j++) {   // ipw[j] = ai^(j + 1)
     ipw[j] = x;
@@ -1172,7 +1124,7 @@ __global__ __launch_bounds__(AGG_T) void lincomb_agg_divide_kernel(LcBatch b, Li
   uint32_t nb8[AGG_E / 4] = {};
 #pragma unroll
   for (int k = 0; k < AGG_E; k++) {
-    const uint32_t v = base + k < nl ? hmod(hmod(acc[k]) * sc) : 0u;   // (acc <= 16 x 16 x 255 + 32)
+    const uint32_t v = base + k < nl ? mod17(mod17(acc[k]) * sc) : 0u;   // (acc <= 16 x 16 x 255 + 32)
     nb8[k >> 2] |= v << (8 * (k & 3));
   }
   lin_div_finish(a, D, cf, sc, av, base, nl, nb8, pt, ipt, carry % HFP);
@@ -1186,7 +1138,7 @@ __global__ __launch_bounds__(256) void divide_general_kernel(const uint8_t* __re
                                                              uint32_t* rem_flag) {
   for (uint64_t i = threadIdx.x; i < nl; i += blockDim.x) rem[i] = num[i];
   __syncthreads();
-  const uint32_t li = hinv(den[dl - 1]);
+  const uint32_t li = hf17::inv(den[dl - 1]);
   for (int64_t i = (int64_t)nl - 1; i >= (int64_t)dl - 1; i--) {
     const uint32_t coeff = rem[i] * li % HFP;
     __syncthreads();
@@ -1247,13 +1199,13 @@ __device__ void scalars_r45(uint8_t* S, uint32_t tz) {
   for (int i = 0; i < 6; i++) rz += cs[i] * ez[i];
   rz %= HFP;
   // constant term of w_z(x), src/plonk.h:584-603
-  uint32_t c = hneg(tz);
-  c += v * hneg(rz);
-  c += g(S_V2) * hneg(az);
-  c += g(S_V3) * hneg(bz);
-  c += g(S_V4) * hneg(cz);
-  c += g(S_V5) * hneg(s1);
-  c += g(S_V6) * hneg(s2);
+  uint32_t c = hf17::neg(tz);
+  c += v * hf17::neg(rz);
+  c += g(S_V2) * hf17::neg(az);
+  c += g(S_V3) * hf17::neg(bz);
+  c += g(S_V4) * hf17::neg(cz);
+  c += g(S_V5) * hf17::neg(s1);
+  c += g(S_V6) * hf17::neg(s2);
   S[S_AB] = (uint8_t)ab;
   S[S_R24] = (uint8_t)r24;
   S[S_BZW] = (uint8_t)bzw;
@@ -1261,7 +1213,7 @@ __device__ void scalars_r45(uint8_t* S, uint32_t tz) {
   S[S_R3B] = (uint8_t)r3b;
   for (int i = 0; i < 6; i++) S[S_VAB + i] = (uint8_t)(v * cs[i] % HFP);   // w_z(x) takes v r(x) term by term
   S[S_RZ] = (uint8_t)rz;
-  S[S_NEGZWZ] = (uint8_t)hneg(zw);
+  S[S_NEGZWZ] = (uint8_t)hf17::neg(zw);
   S[S_W0] = (uint8_t)(c % HFP);
 }
 
@@ -1471,7 +1423,7 @@ __global__ void grand_product_kernel(const uint8_t* __restrict__ vals, uint64_t 
   const uint32_t om = S[S_OMEGA];
   for (int t = threadIdx.x; t < 48; t += blockDim.x) {
     const int k = t / 16, j = t % 16;
-    const uint32_t x = hpow_d(om, j);
+    const uint32_t x = hf17::pow(om, j);
     const uint8_t* p = polys[8 + k];   // s_sigma_1..3
     uint32_t y = 0;
     for (int64_t i = (int64_t)n - 1; i >= 0; i--) y = (y * x + p[i]) % HFP;
@@ -1486,12 +1438,12 @@ __global__ void grand_product_kernel(const uint8_t* __restrict__ vals, uint64_t 
     const uint32_t wa = vals[i - 1], wb = vals[n + i - 1], wc = vals[2 * n + i - 1];
     // hf_pow(omega, i-1) = omega^((i-1) mod 16): OMEGA = 4 is a unit
     const uint32_t j = (uint32_t)((i - 1) & 15);
-    const uint32_t op = hpow_d(om, j);
+    const uint32_t op = hf17::pow(om, j);
     const uint32_t den = (wa + be * op + ga) % HFP * ((wb + be * (k1 * op % HFP) + ga) % HFP) % HFP *
                          ((wc + be * (k2 * op % HFP) + ga) % HFP) % HFP;
     const uint32_t e1 = ev[0][j], e2 = ev[1][j], e3 = ev[2][j];
     const uint32_t num = (wa + be * e1 + ga) % HFP * ((wb + be * e2 + ga) % HFP) % HFP * ((wc + be * e3 + ga) % HFP) % HFP;
-    a = a * (den * hinv(num) % HFP) % HFP;
+    a = a * (den * hf17::inv(num) % HFP) % HFP;
     acc[i] = (uint8_t)a;
   }
 }

@@ -19,11 +19,13 @@
 #include <algorithm>
 
 #include "plk_device.h"
+#include "plk_hf17.h"
 #include "plk_internal.h"
 
 namespace {
 
-constexpr uint32_t HFP = 17;
+constexpr uint32_t HFP = hf17::P;
+using hf17::mod17;   // every call site's bound is noted
 constexpr int PB_WAVES = 4;        // proofs in flight per block
 constexpr int PB_T = PB_WAVES * PLK_WAVE;
 constexpr int NMAX = PLK_PROVE_BATCH_MAX_N;
@@ -32,20 +34,6 @@ constexpr int PL = 72;             // bytes of a long polynomial: lanes 0..63 an
 constexpr int PS = 20;             // a_x b_x c_x z_x and their round-3 factors: at most n + 3 = 19
 constexpr int PM = 36;             // products of two of those, w(x): at most 2n + 3 = 35
 constexpr int NLOG = 2 * NMAX + 4; // SRS logs kept: min(srs_len, 2n + 3)
-
-// x mod 17 for x < 69632 (prove.hip hmod: 61681 = (2^20 + 1) / 17); every call site's bound is noted
-__device__ __forceinline__ uint32_t hmod(uint32_t x) { return x - 17u * (__umul24(x, 61681u) >> 20); }
-__device__ __forceinline__ uint32_t hneg(uint32_t a) { return a ? HFP - a : 0; }
-__device__ __forceinline__ uint32_t hpw(uint32_t b, uint32_t e) {   // b < 17; 0^0 = 1 (hf_pow)
-  uint32_t r = 1;
-  for (int k = 0; k < 7; k++) {   // e < 128
-    if (e & 1u) r = hmod(r * b);
-    b = hmod(b * b);
-    e >>= 1;
-  }
-  return r;
-}
-__device__ __forceinline__ uint32_t hinv(uint32_t a) { return hpw(a, HFP - 2); }   // inv(0) = 0 (hf.h LUT)
 
 #define NEW_PHASE(lane) asm volatile("" : "+v"(lane))
 
@@ -111,7 +99,7 @@ __device__ __forceinline__ void mul_store(const uint8_t* a, int la, const uint8_
                                           int lane) {
   uint32_t s = 0;
   conv1(a, la, b, lb, lane, s);   // <= 19 * 256
-  if (lane < cap) out[lane] = (uint8_t)hmod(s);
+  if (lane < cap) out[lane] = (uint8_t)mod17(s);
 }
 
 // trimmed length (poly_new_internal, src/poly.h:20-38: at least 1) of the polynomial whose coefficient
@@ -156,7 +144,7 @@ __global__ __launch_bounds__(PB_T, 8) void prove_batch_kernel(PlkProveBatch a) {
   const int lr3 = lzx + n - 1;
   const int lw = max(max(part, max(lhi, 1)), max(max(n, lzx), max(lr3, la)));
   const int lwq = lw - 1, lwo = lzx - 1;
-  const uint32_t invlead = hinv(T.zh[lz - 1]);
+  const uint32_t invlead = hf17::inv_canon(T.zh[lz - 1]);
   const uint64_t srs_len = a.srs_len;
 
   for (uint32_t e = blockIdx.x * PB_WAVES + wv; e < a.batch; e += gridDim.x * PB_WAVES) {
@@ -181,7 +169,7 @@ __global__ __launch_bounds__(PB_T, 8) void prove_batch_kernel(PlkProveBatch a) {
         const uint32_t qm = M.cir[lane], ql = M.cir[n + lane], qr = M.cir[2 * n + lane], qo = M.cir[3 * n + lane],
                        qc = M.cir[4 * n + lane];
         const uint32_t wa = M.cir[11 * n + lane], wb = M.cir[12 * n + lane], wc = M.cir[13 * n + lane];
-        bad = hmod(ql * wa + qr * wb + qo * wc + qm * hmod(wa * wb) + qc);   // <= 4 * 256 + 16
+        bad = mod17(ql * wa + qr * wb + qo * wc + qm * mod17(wa * wb) + qc);   // <= 4 * 256 + 16
         M.vals[0][lane] = (uint8_t)wa; M.vals[1][lane] = (uint8_t)wb; M.vals[2][lane] = (uint8_t)wc;
         M.vals[3][lane] = (uint8_t)qo; M.vals[4][lane] = (uint8_t)qm; M.vals[5][lane] = (uint8_t)ql;
         M.vals[6][lane] = (uint8_t)qr; M.vals[7][lane] = (uint8_t)qc;
@@ -206,16 +194,16 @@ __global__ __launch_bounds__(PB_T, 8) void prove_batch_kernel(PlkProveBatch a) {
           const int v = it >> 4, r = it & 15;
           uint32_t s = 0;
           for (int c = 0; c < n; c++) s += T.hinvm[(r < n ? r : 0) * n + c] * M.vals[v][c];   // <= 16 * 256
-          M.in[v][r] = r < n ? (uint8_t)hmod(s) : 0;
+          M.in[v][r] = r < n ? (uint8_t)mod17(s) : 0;
         }
         if (lane < NMAX) M.in[IN_L1][lane] = lane < n ? T.hinvm[lane * n] : 0;   // interpolate_at_h(e_0)
         wsync();
         // round 2's grand product (src/plonk.h:326-359)
         if (lane < 3 * NMAX) {
           const int k = lane >> 4, j = lane & 15;
-          const uint32_t x = hpw(4, (uint32_t)j);
+          const uint32_t x = hf17::pow_canon(4, (uint32_t)j);
           uint32_t y = 0;
-          for (int i = n - 1; i >= 0; i--) y = hmod(y * x + M.in[IN_S1 + k][i]);
+          for (int i = n - 1; i >= 0; i--) y = mod17(y * x + M.in[IN_S1 + k][i]);
           M.ev[k][j] = (uint8_t)y;
         }
         wsync();
@@ -224,27 +212,27 @@ __global__ __launch_bounds__(PB_T, 8) void prove_batch_kernel(PlkProveBatch a) {
           uint32_t r = 1;
           if (lane >= 1 && lane < n) {
             const int j = lane - 1;
-            const uint32_t wa = M.vals[0][j], wb = M.vals[1][j], wc = M.vals[2][j], op = hpw(4, (uint32_t)j);
-            const uint32_t den = hmod(hmod(hmod(wa + be * op + ga) * hmod(wb + be * hmod(2 * op) + ga)) *
-                                      hmod(wc + be * hmod(3 * op) + ga));
-            const uint32_t num = hmod(hmod(hmod(wa + be * M.ev[0][j] + ga) * hmod(wb + be * M.ev[1][j] + ga)) *
-                                      hmod(wc + be * M.ev[2][j] + ga));
-            r = hmod(den * hinv(num));
+            const uint32_t wa = M.vals[0][j], wb = M.vals[1][j], wc = M.vals[2][j], op = hf17::pow_canon(4, (uint32_t)j);
+            const uint32_t den = mod17(mod17(mod17(wa + be * op + ga) * mod17(wb + be * mod17(2 * op) + ga)) *
+                                      mod17(wc + be * mod17(3 * op) + ga));
+            const uint32_t num = mod17(mod17(mod17(wa + be * M.ev[0][j] + ga) * mod17(wb + be * M.ev[1][j] + ga)) *
+                                      mod17(wc + be * M.ev[2][j] + ga));
+            r = mod17(den * hf17::inv_canon(num));
           }
           if (lane < NMAX) M.ratio[lane] = (uint8_t)r;
           wsync();
           uint32_t acc = 1;
-          for (int i = 1; i < n; i++) acc = i <= lane ? hmod(acc * M.ratio[i]) : acc;
+          for (int i = 1; i < n; i++) acc = i <= lane ? mod17(acc * M.ratio[i]) : acc;
           wsync();
           if (lane < NMAX) M.ratio[lane] = lane < n ? (uint8_t)acc : 0;   // acc over H
           wsync();
           uint32_t s = 0;
           if (lane < NMAX)
             for (int c = 0; c < n; c++) s += T.hinvm[(lane < n ? lane : 0) * n + c] * M.ratio[c];
-          const uint32_t ax = lane < n ? hmod(s) : 0;
+          const uint32_t ax = lane < n ? mod17(s) : 0;
           if (lane < NMAX) M.in[IN_ACC][lane] = (uint8_t)ax;
           // acc_x(omega^n) must be 1 (src/plonk.h:366-368)
-          accw = hmod(plk_wave_sum(ax * hpw(hpw(4, (uint32_t)n), (uint32_t)lane & 15u)));   // <= 16 * 256
+          accw = mod17(plk_wave_sum(ax * hf17::pow_canon(hf17::pow_canon(4, (uint32_t)n), (uint32_t)lane & 15u)));   // <= 16 * 256
         }
       }
     } else {
@@ -265,29 +253,29 @@ __global__ __launch_bounds__(PB_T, 8) void prove_batch_kernel(PlkProveBatch a) {
       const uint32_t al = ch[0] % HFP, be = ch[1] % HFP, ga = ch[2] % HFP, z = ch[3] % HFP, v = ch[4] % HFP;
       uint32_t b[9];
       for (int i = 0; i < 9; i++) b[i] = rd[i] % HFP;
-      const uint32_t al2 = hmod(al * al), bk1 = hmod(be * 2), bk2 = hmod(be * 3);
+      const uint32_t al2 = mod17(al * al), bk1 = mod17(be * 2), bk2 = mod17(be * 3);
       // ---- rounds 1-2: a_x = (b2 + b1 x) Z_H + f_a, ..., z_x = (b9 + b8 x + b7 x^2) Z_H + acc_x
       const uint32_t zh0 = lane < lz ? T.zh[lane] : 0, zh1 = lane >= 1 && lane - 1 < lz ? T.zh[lane - 1] : 0,
                      zh2 = lane >= 2 && lane - 2 < lz ? T.zh[lane - 2] : 0;
       const uint32_t inl = lane < n ? 1u : 0u;
       const int li = lane < NMAX ? lane : 0;
-      const uint32_t ax = lane < la ? hmod(b[1] * zh0 + b[0] * zh1 + inl * M.in[IN_FA][li]) : 0;
-      const uint32_t bx = lane < la ? hmod(b[3] * zh0 + b[2] * zh1 + inl * M.in[IN_FB][li]) : 0;
-      const uint32_t cx = lane < la ? hmod(b[5] * zh0 + b[4] * zh1 + inl * M.in[IN_FC][li]) : 0;
-      const uint32_t zx = lane < lzx ? hmod(b[8] * zh0 + b[7] * zh1 + b[6] * zh2 + inl * M.in[IN_ACC][li]) : 0;
+      const uint32_t ax = lane < la ? mod17(b[1] * zh0 + b[0] * zh1 + inl * M.in[IN_FA][li]) : 0;
+      const uint32_t bx = lane < la ? mod17(b[3] * zh0 + b[2] * zh1 + inl * M.in[IN_FB][li]) : 0;
+      const uint32_t cx = lane < la ? mod17(b[5] * zh0 + b[4] * zh1 + inl * M.in[IN_FC][li]) : 0;
+      const uint32_t zx = lane < lzx ? mod17(b[8] * zh0 + b[7] * zh1 + b[6] * zh2 + inl * M.in[IN_ACC][li]) : 0;
       const uint32_t s1 = inl * M.in[IN_S1][li], s2 = inl * M.in[IN_S2][li], s3 = inl * M.in[IN_S3][li];
       const uint32_t c0 = lane == 0, c1 = lane == 1;
       if (lane < PS) {
         M.A[lane] = (uint8_t)ax; M.B[lane] = (uint8_t)bx; M.C[lane] = (uint8_t)cx; M.Z[lane] = (uint8_t)zx;
         // round 3's linear factors (src/plonk.h:409-489)
-        M.A2[lane] = (uint8_t)hmod(al * hmod(ax + c0 * ga + c1 * be));
-        M.B2[lane] = (uint8_t)hmod(bx + c0 * ga + c1 * bk1);
-        M.C2[lane] = (uint8_t)hmod(cx + c0 * ga + c1 * bk2);
-        M.A3[lane] = (uint8_t)hmod(al * hmod(ax + be * s1 + c0 * ga));
-        M.B3[lane] = (uint8_t)hmod(bx + be * s2 + c0 * ga);
-        M.C3[lane] = (uint8_t)hmod(cx + be * s3 + c0 * ga);
-        M.ZW[lane] = (uint8_t)hmod(zx * hpw(4, (uint32_t)lane & 15u));   // z(omega x), OMEGA = 4
-        M.Z1[lane] = (uint8_t)hmod(al2 * hmod(zx + c0 * 16u));
+        M.A2[lane] = (uint8_t)mod17(al * mod17(ax + c0 * ga + c1 * be));
+        M.B2[lane] = (uint8_t)mod17(bx + c0 * ga + c1 * bk1);
+        M.C2[lane] = (uint8_t)mod17(cx + c0 * ga + c1 * bk2);
+        M.A3[lane] = (uint8_t)mod17(al * mod17(ax + be * s1 + c0 * ga));
+        M.B3[lane] = (uint8_t)mod17(bx + be * s2 + c0 * ga);
+        M.C3[lane] = (uint8_t)mod17(cx + be * s3 + c0 * ga);
+        M.ZW[lane] = (uint8_t)mod17(zx * hf17::pow_canon(4, (uint32_t)lane & 15u));   // z(omega x), OMEGA = 4
+        M.Z1[lane] = (uint8_t)mod17(al2 * mod17(zx + c0 * 16u));
       }
       const uint32_t la_t = max(max(trimmed(ax), trimmed(bx)), trimmed(cx));
       if (la_t > srs_len) st = exit_word(X_SRS);
@@ -317,7 +305,7 @@ __global__ __launch_bounds__(PB_T, 8) void prove_batch_kernel(PlkProveBatch a) {
         conv2(M.T2a, lab, M.T2b, l2b, lane, p0, p1);             // t_2               <= 35 * 256
         conv2(M.T3a, lab, M.T3b, l2b, lane, m0, m1);             // t_3               <= 35 * 256
         p0 += inl * M.in[IN_QC][li];                             // total <= 5 * 4096 + 8960 + 16 + 16 < 69632
-        uint32_t r0 = hmod(p0 + hneg(hmod(m0))), r1 = hmod(p1 + hneg(hmod(m1)));
+        uint32_t r0 = mod17(p0 + hf17::neg(mod17(m0))), r1 = mod17(p1 + hf17::neg(mod17(m1)));
         if (lane + 64 >= lnum) r1 = 0;
         // ---- t(x) = numerator / Z_H: the reference's loop, one quotient coefficient per step
         uint32_t q0 = 0;   // (ltx <= 4n - 4 = 60 coefficients: one per lane)
@@ -325,12 +313,12 @@ __global__ __launch_bounds__(PB_T, 8) void prove_batch_kernel(PlkProveBatch a) {
         for (int k = ltx - 1; k >= 0; k--) {
           const int idx = k + lz - 1;
           const uint32_t top = (uint32_t)__shfl((int)(idx < 64 ? r0 : r1), idx & 63, 64);
-          const uint32_t q = hmod(top * invlead);
+          const uint32_t q = mod17(top * invlead);
           if (lane == k) q0 = q;
           const uint32_t d0 = (uint32_t)(lane - k), d1 = d0 + 64u;
-          const uint32_t nq = hneg(q);
-          r0 = hmod(r0 + nq * (d0 < (uint32_t)lz ? T.zh[d0] : 0u));
-          r1 = hmod(r1 + nq * (d1 < (uint32_t)lz ? T.zh[d1] : 0u));
+          const uint32_t nq = hf17::neg(q);
+          r0 = mod17(r0 + nq * (d0 < (uint32_t)lz ? T.zh[d0] : 0u));
+          r1 = mod17(r1 + nq * (d1 < (uint32_t)lz ? T.zh[d1] : 0u));
         }
         const bool rem_t = __ballot((r0 | r1) != 0) != 0;   // what is left is the remainder (degree < lz - 1)
         M.TX[lane] = (uint8_t)q0;
@@ -349,8 +337,8 @@ __global__ __launch_bounds__(PB_T, 8) void prove_batch_kernel(PlkProveBatch a) {
           NEW_PHASE(lane);
           // ---- round 4: evaluations at z (src/plonk.h:527-574); evaluation is a ring homomorphism, so
           // r_z comes from r(x)'s terms (prove.hip scalars_r45)
-          const uint32_t zp = hpw(z, (uint32_t)lane);   // z^lane, 0^0 = 1
-          auto ev = [&](uint32_t coef) { return hmod(plk_wave_sum(coef * zp)); };   // <= 64 * 256
+          const uint32_t zp = hf17::pow_canon(z, (uint32_t)lane);   // z^lane, 0^0 = 1
+          auto ev = [&](uint32_t coef) { return mod17(plk_wave_sum(coef * zp)); };   // <= 64 * 256
           const int ls = lane < PS ? lane : 0, li = lane < NMAX ? lane : 0;
           const uint32_t inl = lane < n ? 1u : 0u, c0 = lane == 0;
           const uint32_t ax = lane < la ? M.A[ls] : 0u, bx = lane < la ? M.B[ls] : 0u, cx = lane < la ? M.C[ls] : 0u,
@@ -361,35 +349,35 @@ __global__ __launch_bounds__(PB_T, 8) void prove_batch_kernel(PlkProveBatch a) {
                          qo = inl * M.in[IN_QO][li], l1 = inl * M.in[IN_L1][li];
           const uint32_t az = ev(ax), bz = ev(bx), cz = ev(cx), s1z = ev(s1), s2z = ev(s2), tz = ev(q0), zwz = ev(zwx),
                          l1z = ev(l1);
-          const uint32_t abz = hmod(az * bz);
-          const uint32_t x1 = hmod(az + be * z + ga), x2 = hmod(bz + hmod(be * 2) * z + ga),
-                         x3 = hmod(cz + hmod(be * 3) * z + ga);
-          const uint32_t r2 = hmod(hmod(hmod(x1 * x2) * x3) * al);
-          const uint32_t r24 = hmod(r2 + hmod(l1z * al2));
-          const uint32_t y1 = hmod(az + be * s1z + ga), y2 = hmod(bz + be * s2z + ga);
-          const uint32_t r3b = hmod(hmod(hmod(y1 * y2) * al) * hmod(be * zwz));
+          const uint32_t abz = mod17(az * bz);
+          const uint32_t x1 = mod17(az + be * z + ga), x2 = mod17(bz + mod17(be * 2) * z + ga),
+                         x3 = mod17(cz + mod17(be * 3) * z + ga);
+          const uint32_t r2 = mod17(mod17(mod17(x1 * x2) * x3) * al);
+          const uint32_t r24 = mod17(r2 + mod17(l1z * al2));
+          const uint32_t y1 = mod17(az + be * s1z + ga), y2 = mod17(bz + be * s2z + ga);
+          const uint32_t r3b = mod17(mod17(mod17(y1 * y2) * al) * mod17(be * zwz));
           // r(x), coefficient `lane` (at most lr3 <= 34 coefficients)
-          const uint32_t rx = hmod(abz * qm + az * ql + bz * qr + cz * qo + r24 * zx + r3b * p3);   // <= 6 * 256
+          const uint32_t rx = mod17(abz * qm + az * ql + bz * qr + cz * qo + r24 * zx + r3b * p3);   // <= 6 * 256
           const uint32_t rz = ev(rx);
           // ---- round 5: w_z(x) and w_z_omega(x) (src/plonk.h:580-621)
-          const uint32_t zn2 = hpw(z, (uint32_t)n + 2u), z2n4 = hpw(z, 2u * (uint32_t)n + 4u);
-          const uint32_t v2 = hmod(v * v), v3 = hmod(v2 * v), v4 = hmod(v3 * v), v5 = hmod(v4 * v), v6 = hmod(v5 * v);
-          const uint32_t w0 = hmod(hneg(tz) + v * hneg(rz) + v2 * hneg(az) + v3 * hneg(bz) + v4 * hneg(cz) +
-                                   v5 * hneg(s1z) + v6 * hneg(s2z));
-          const uint32_t wx = hmod(tlo + zn2 * tmid + z2n4 * thi + v * rx + v2 * ax + v3 * bx + v4 * cx + v5 * s1 +
+          const uint32_t zn2 = hf17::pow_canon(z, (uint32_t)n + 2u), z2n4 = hf17::pow_canon(z, 2u * (uint32_t)n + 4u);
+          const uint32_t v2 = mod17(v * v), v3 = mod17(v2 * v), v4 = mod17(v3 * v), v5 = mod17(v4 * v), v6 = mod17(v5 * v);
+          const uint32_t w0 = mod17(hf17::neg(tz) + v * hf17::neg(rz) + v2 * hf17::neg(az) + v3 * hf17::neg(bz) + v4 * hf17::neg(cz) +
+                                   v5 * hf17::neg(s1z) + v6 * hf17::neg(s2z));
+          const uint32_t wx = mod17(tlo + zn2 * tmid + z2n4 * thi + v * rx + v2 * ax + v3 * bx + v4 * cx + v5 * s1 +
                                    v6 * s2 + c0 * w0);   // <= 9 * 256 + 32
-          const uint32_t zz = hmod(zx + c0 * hneg(zwz));
+          const uint32_t zz = mod17(zx + c0 * hf17::neg(zwz));
           if (lane < PM) { M.W[lane] = (uint8_t)wx; M.Q[lane] = (uint8_t)zz; }
           wsync();
           // quotient coefficient `lane` of the division by x - c: sum_{j > lane} p[j] c^(j - lane - 1)
-          const uint32_t zo = hmod(z * 4);
+          const uint32_t zo = mod17(z * 4);
           uint32_t wq = 0, wo = 0;
-          for (int j = lw - 1; j >= 1; j--) wq = j > lane ? hmod(wq * z + M.W[j]) : wq;
-          for (int j = lzx - 1; j >= 1; j--) wo = j > lane ? hmod(wo * zo + M.Q[j]) : wo;
+          for (int j = lw - 1; j >= 1; j--) wq = j > lane ? mod17(wq * z + M.W[j]) : wq;
+          for (int j = lzx - 1; j >= 1; j--) wo = j > lane ? mod17(wo * zo + M.Q[j]) : wo;
           if (lane >= lwq) wq = 0;
           if (lane >= lwo) wo = 0;
           const uint32_t rem1 = ev(wx);                                        // w(z)
-          const uint32_t rem2 = hmod(plk_wave_sum(zz * hpw(zo, (uint32_t)lane)));   // (z_x - z_omega_z)(z omega)
+          const uint32_t rem2 = mod17(plk_wave_sum(zz * hf17::pow_canon(zo, (uint32_t)lane)));   // (z_x - z_omega_z)(z omega)
           if (a.strict && rem1) st = exit_word(X_REM_W1);
           else if (a.strict && rem2) st = exit_word(X_REM_W2);
           else if (max(trimmed(wq), trimmed(wo)) > srs_len) st = exit_word(X_SRS);
