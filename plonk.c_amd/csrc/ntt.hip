@@ -10,31 +10,23 @@
 //   forward  DIF (Gentleman-Sande), natural order in  -> bit-reversed out
 //   pointwise product in bit-reversed order
 //   inverse  DIT (Cooley-Tukey),   bit-reversed in   -> natural order out, times N^-1
-// A size-2^k transform is cut into passes over disjoint bit ranges [lo, lo+M) of the index;
-// one pass = one launch whose workgroups each own a tile of 2^M rows (the butterfly bits)
-// x C columns (consecutive low-bit values when lo > 0, consecutive groups when lo = 0),
-// staged once through LDS and run through all M radix-2 stages there.
-// Twiddles factor into a universal per-stage table T[2^j + r] = w_{2^(j+1)}^r (independent
-// of N) times a per-column factor F[c][j] = w_{2^27}^(L * 2^(26-lo-j)) (1 when lo = 0).
+// Stage twiddles come from one table T[2^j + r] = w_{2^(j+1)}^r, independent of N.
 //
-// poly_mul plan at 2^k > 2^12 (3 launches for k <= 23):
-//   ntt_pass_kernel   forward passes over the high bits, reading the u8 inputs directly
-//   ntt_center_kernel last forward pass (lo = 0) of a AND b, pointwise product, first
-//                     inverse pass -- one tile, one LDS round trip
-//   ntt_pass_kernel   inverse passes over the high bits; the last one scales by N^-1,
-//                     leaves Montgomery form, reduces mod 17, stores bytes and records the
-//                     last non-zero index for the reference's trailing-zero trim
-// k <= 12: one workgroup does everything (polymul_small_kernel); min(la, lb) <= 32: direct
-// convolution (polymul_direct_kernel).
+// Plan of a product of la x lb coefficients (plk_poly_mul_launch):
+//   direct       min(la, lb) <= PLK_DIRECT_MAX: schoolbook convolution (polymul_direct_kernel)
+//   one workgroup  2^k <= 2^PLK_SMALL_LOG points: both forward transforms, the pointwise product,
+//                the inverse and the byte output in LDS (polymul_small_kernel)
+//   blocked      operands outside one transform's exact range: piece products accumulated mod 17
+//                (blocked_launch)
+//   everything above 2^12 points goes to the tile engine in ntt_wave.hip (ntt_group)
+// Standalone transforms (plk_ntt_launch) of 2^k <= 2^12 points run in one workgroup
+// (ntt_pass_kernel); larger ones go to the tile engine too.
 #include "plk_device.h"
 #include "plk_internal.h"
 
-#include <chrono>
-
 #include <stdio.h>
-#include <stdlib.h>
 
-#include <algorithm>
+#include <chrono>
 #include <vector>
 
 __constant__ uint32_t c_mont17[17];            // v * R mod p for v = 0..16
@@ -56,114 +48,38 @@ struct Tw {
   const uint32_t* hi;      // w_{2^27}^(4096 i), i < 2^15
 };
 
-__device__ __forceinline__ uint32_t root27(const Tw& t, uint32_t e) {  // w_{2^27}^e, e < 2^27
-  return bb::mmul(t.lo[e & 4095u], t.hi[e >> 12]);
-}
-
-// Tile geometry of one pass
-struct Pass {
-  int k;       // log2 N
-  int lo;      // lowest bit of this pass
-  int M;       // bits in this pass (rows = 2^M)
-  int C;       // columns per tile (power of two; >= 4 when lo > 0)
-};
-
-// global index of (row r, column c) of tile t
-__device__ __forceinline__ uint64_t tile_index(const Pass& p, uint32_t t, int r, int c) {
-  if (p.lo == 0) return (((uint64_t)t * p.C + c) << p.M) | (uint64_t)r;
-  const uint32_t per_h = (1u << p.lo) / p.C;
-  const uint64_t H = t / per_h;
-  const uint32_t L = (t % per_h) * p.C + c;
-  return (H << (p.lo + p.M)) | ((uint64_t)r << p.lo) | L;
-}
-
-// F[c][j] = w_{2^27}^(L * 2^(26-lo-j)) for the tile's columns (only when lo > 0)
-__device__ void column_factors(const Pass& p, uint32_t t, const Tw& tw, uint32_t* F) {
-  if (p.lo == 0) return;
-  const uint32_t per_h = (1u << p.lo) / p.C;
-  for (int c = threadIdx.x; c < p.C; c += blockDim.x) {
-    const uint32_t L = (t % per_h) * p.C + c;
-    uint32_t f = root27(tw, L << (27 - p.lo - p.M));      // stage j = M-1
-    for (int j = p.M - 1; j >= 0; j--) {
-      F[c * p.M + j] = f;
-      f = bb::mmul(f, f);
-    }
-  }
-}
-
-// ---- global <-> LDS tile movement, 4 elements per thread-step --------------------------
-// lo == 0: the tile is C contiguous runs of 2^M; 4 consecutive rows of one column.
-// lo  > 0: rows of C contiguous elements; 4 consecutive columns of one row.
-// LDS layout X[c * RS + phys(r)], RS = col_stride(2^M).
-template <bool U8>
-__device__ __forceinline__ void load_tile(const Pass& p, uint32_t t, uint32_t* X, int RS, const uint32_t* d,
-                                          const uint8_t* s8, uint64_t ls) {
-  const int rows = 1 << p.M;
-  if (p.lo == 0 && p.M < 2) {                  // tiny single-pass transforms
-    for (int e = threadIdx.x; e < rows * p.C; e += blockDim.x) {
-      const int r = e & (rows - 1), c = e >> p.M;
-      const uint64_t idx = tile_index(p, t, r, c);
-      X[c * RS + phys(r)] = U8 ? (idx < ls ? c_mont17[s8[idx] % 17u] : 0u) : d[idx];
-    }
+// ---- global <-> LDS movement of an array of 2^k words, 4 per thread-step ----------------
+// LDS layout X[phys(r)].
+__device__ __forceinline__ void load_array(int k, uint32_t* X, const uint32_t* d) {
+  const int n = 1 << k;
+  if (k < 2) {                                 // fewer than 4 words
+    for (int r = threadIdx.x; r < n; r += blockDim.x) X[phys(r)] = d[r];
     return;
   }
-  const int E4 = (rows * p.C) >> 2;
-  for (int e = threadIdx.x; e < E4; e += blockDim.x) {
-    int r, c;
-    bool colrun;
-    if (p.lo == 0) { c = (4 * e) >> p.M; r = (4 * e) & (rows - 1); colrun = true; }
-    else { r = (4 * e) / p.C; c = (4 * e) % p.C; colrun = false; }
-    const uint64_t idx = tile_index(p, t, r, c);
-    uint32_t v[4];
-    if (U8) {
-#pragma unroll
-      for (int i = 0; i < 4; i++) v[i] = idx + i < ls ? c_mont17[s8[idx + i] % 17u] : 0u;
-    } else {
-      const uint4 q = *reinterpret_cast<const uint4*>(d + idx);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    }
-    if (colrun) {
-#pragma unroll
-      for (int i = 0; i < 4; i++) X[c * RS + phys(r) + i] = v[i];   // r % 4 == 0: one 32-row block
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; i++) X[(c + i) * RS + phys(r)] = v[i];
-    }
+  for (int e = threadIdx.x; e < n >> 2; e += blockDim.x) {
+    const uint4 q = *reinterpret_cast<const uint4*>(d + 4 * e);
+    uint32_t* x = X + phys(4 * e);             // (4 e .. 4 e + 3: one 32-row block)
+    x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
   }
 }
 
-__device__ __forceinline__ void store_tile(const Pass& p, uint32_t t, const uint32_t* X, int RS, uint32_t* d) {
-  const int rows = 1 << p.M;
-  if (p.lo == 0 && p.M < 2) {
-    for (int e = threadIdx.x; e < rows * p.C; e += blockDim.x) {
-      const int r = e & (rows - 1), c = e >> p.M;
-      d[tile_index(p, t, r, c)] = X[c * RS + phys(r)];
-    }
+__device__ __forceinline__ void store_array(int k, const uint32_t* X, uint32_t* d) {
+  const int n = 1 << k;
+  if (k < 2) {
+    for (int r = threadIdx.x; r < n; r += blockDim.x) d[r] = X[phys(r)];
     return;
   }
-  const int E4 = (rows * p.C) >> 2;
-  for (int e = threadIdx.x; e < E4; e += blockDim.x) {
-    int r, c;
-    uint4 q;
-    if (p.lo == 0) {
-      c = (4 * e) >> p.M; r = (4 * e) & (rows - 1);
-      const uint32_t* x = X + c * RS + phys(r);
-      q = make_uint4(x[0], x[1], x[2], x[3]);
-    } else {
-      r = (4 * e) / p.C; c = (4 * e) % p.C;
-      const int pr = phys(r);
-      q = make_uint4(X[c * RS + pr], X[(c + 1) * RS + pr], X[(c + 2) * RS + pr], X[(c + 3) * RS + pr]);
-    }
-    *reinterpret_cast<uint4*>(d + tile_index(p, t, r, c)) = q;
+  for (int e = threadIdx.x; e < n >> 2; e += blockDim.x) {
+    const uint32_t* x = X + phys(4 * e);
+    *reinterpret_cast<uint4*>(d + 4 * e) = make_uint4(x[0], x[1], x[2], x[3]);
   }
 }
 
 // ---- radix-2^R rounds in registers -------------------------------------------------------
 // DIF stages j, j-1, .., j-R+1 on the 2^R elements {base + k 2^(j-R+1)} of one column:
-// (u, v) -> (u + v, (u - v) w), w = T[2^s + (row mod 2^s)] (* F[c][s] when lo > 0).
+// (u, v) -> (u + v, (u - v) w), w = T[2^s + (row mod 2^s)].
 template <int R, bool INV>
-__device__ __forceinline__ void round_r(uint32_t* X, int M, int C, int RS, int top, const uint32_t* Tsm,
-                                       const uint32_t* F, bool has_f) {
+__device__ __forceinline__ void round_r(uint32_t* X, int M, int C, int RS, int top, const uint32_t* Tsm) {
   constexpr int NE = 1 << R;
   const int lowbit = INV ? top : top - R + 1;      // lowest stage bit of this round
   const int hstride = 1 << lowbit;
@@ -185,8 +101,7 @@ __device__ __forceinline__ void round_r(uint32_t* X, int M, int C, int RS, int t
       for (int k = 0; k < NE; k++) {
         if (k & hk) continue;
         const int rr = (base + k * hstride) & ((1 << s) - 1);
-        uint32_t w = Tsm[(1 << s) + rr];
-        if (has_f) w = bb::mmul(w, F[c * M + s]);
+        const uint32_t w = Tsm[(1 << s) + rr];
         const uint32_t u = v[k], x = v[k + hk];
         if (!INV) {
           v[k] = bb::madd(u, x);
@@ -204,77 +119,43 @@ __device__ __forceinline__ void round_r(uint32_t* X, int M, int C, int RS, int t
   __syncthreads();
 }
 
-// All M stages of a tile: DIF top-down / DIT bottom-up, in rounds of up to 4 stages.
+// All M stages of C columns of 2^M words in LDS (column c at X + c RS): DIF top-down / DIT
+// bottom-up, in rounds of up to 4 stages.
 template <bool INV>
-__device__ void tile_stages(uint32_t* X, int M, int C, int RS, const uint32_t* Tsm, const uint32_t* F,
-                            bool has_f) {
+__device__ void tile_stages(uint32_t* X, int M, int C, int RS, const uint32_t* Tsm) {
   int done = 0;
   while (done < M) {
     const int left = M - done;
     const int R = left >= 4 ? 4 : left;
     const int top = INV ? done : (M - 1 - done);
     switch (R) {
-      case 4: round_r<4, INV>(X, M, C, RS, top, Tsm, F, has_f); break;
-      case 3: round_r<3, INV>(X, M, C, RS, top, Tsm, F, has_f); break;
-      case 2: round_r<2, INV>(X, M, C, RS, top, Tsm, F, has_f); break;
-      default: round_r<1, INV>(X, M, C, RS, top, Tsm, F, has_f); break;
+      case 4: round_r<4, INV>(X, M, C, RS, top, Tsm); break;
+      case 3: round_r<3, INV>(X, M, C, RS, top, Tsm); break;
+      case 2: round_r<2, INV>(X, M, C, RS, top, Tsm); break;
+      default: round_r<1, INV>(X, M, C, RS, top, Tsm); break;
     }
     done += R;
   }
 }
 
-}  // namespace
-
-
-// Input/output modes of a pass
-enum : int { IN_U32 = 0, IN_U8 = 1 };
-enum : int { OUT_U32 = 0, OUT_U8 = 1 };
-
-// One NTT pass over 1 or 2 arrays (blockIdx.y).  IN_U8: arrays are byte vectors of length
-// la / lb (zero-padded, reduced mod 17, converted to Montgomery).  OUT_U8: the final inverse
-// pass: scale by N^-1 given in normal form (which also leaves Montgomery form), mod 17,
-// bytes to out8 for idx < out_len; max non-zero idx + 1 -> *nz (atomicMax).
-template <bool INV, int IN, int OUT>
-__global__ __launch_bounds__(NTT_THREADS) void ntt_pass_kernel(
-    Pass p, uint32_t* d0, uint32_t* d1, const uint8_t* a8, const uint8_t* b8, uint64_t la, uint64_t lb,
-    Tw tw, uint8_t* out8, uint64_t out_len, uint32_t ninv, uint32_t* nz) {
+// A standalone transform of 2^k <= 2^12 words, in place, by one workgroup: the array staged in
+// LDS, all k radix-2 stages there; forward (DIF, natural -> bit-reversed) or inverse (DIT,
+// bit-reversed -> natural, unscaled) with `small` the forward or inverse stage table.
+template <bool INV>
+__global__ __launch_bounds__(NTT_THREADS) void ntt_pass_kernel(int k, uint32_t* d, const uint32_t* small) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const int rows = 1 << p.M;
-  const int RS = col_stride(rows);
+  const int n = 1 << k;
+  const int RS = col_stride(n);
   uint32_t* X = smem;
-  uint32_t* Tsm = X + p.C * RS;
-  uint32_t* F = Tsm + rows;
-  uint32_t* d = blockIdx.y == 0 ? d0 : d1;
-  const uint32_t t = blockIdx.x;
-
-  for (int i = threadIdx.x; i < rows; i += blockDim.x) Tsm[i] = tw.small[i];
-  column_factors(p, t, tw, F);
-  if (IN == IN_U8) load_tile<true>(p, t, X, RS, nullptr, blockIdx.y == 0 ? a8 : b8, blockIdx.y == 0 ? la : lb);
-  else load_tile<false>(p, t, X, RS, d, nullptr, 0);
+  uint32_t* Tsm = X + RS;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) Tsm[i] = small[i];
+  load_array(k, X, d);
   __syncthreads();
-  tile_stages<INV>(X, p.M, p.C, RS, Tsm, F, p.lo != 0);
-
-  if (OUT == OUT_U32) {
-    store_tile(p, t, X, RS, d);
-    return;
-  }
-  uint32_t last = 0;
-  const int E = rows * p.C;
-  for (int e = threadIdx.x; e < E; e += blockDim.x) {
-    int r, c;
-    if (p.lo == 0) { r = e & (rows - 1); c = e >> p.M; }
-    else { c = e % p.C; r = e / p.C; }
-    const uint64_t idx = tile_index(p, t, r, c);
-    if (idx < out_len) {
-      const uint8_t byte = (uint8_t)(bb::mmul(X[c * RS + phys(r)], ninv) % 17u);
-      out8[idx] = byte;
-      if (byte && (uint32_t)idx + 1 > last) last = (uint32_t)idx + 1;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) last = max(last, (uint32_t)__shfl_xor(last, off, PLK_WAVE));
-  if ((threadIdx.x & (PLK_WAVE - 1)) == 0 && last) atomicMax(nz, last);
+  tile_stages<INV>(X, k, 1, RS, Tsm);
+  store_array(k, X, d);
 }
+
+}  // namespace
 
 // Whole poly_mul in one workgroup for N = 2^k <= 2^PLK_SMALL_LOG.
 __global__ __launch_bounds__(1024) void polymul_small_kernel(const uint8_t* a8, uint64_t la, const uint8_t* b8,
@@ -295,12 +176,12 @@ __global__ __launch_bounds__(1024) void polymul_small_kernel(const uint8_t* a8, 
   }
   __syncthreads();
   if (k > 0) {
-    tile_stages<false>(X, k, 1, RS, Tf, nullptr, false);
-    tile_stages<false>(Y, k, 1, RS, Tf, nullptr, false);
+    tile_stages<false>(X, k, 1, RS, Tf);
+    tile_stages<false>(Y, k, 1, RS, Tf);
   }
   for (int i = threadIdx.x; i < N; i += blockDim.x) X[phys(i)] = bb::mmul(X[phys(i)], Y[phys(i)]);
   __syncthreads();
-  if (k > 0) tile_stages<true>(X, k, 1, RS, Ti, nullptr, false);
+  if (k > 0) tile_stages<true>(X, k, 1, RS, Ti);
   const uint64_t rl = la + lb - 1;
   uint32_t last = 0;
   for (int i = threadIdx.x; i < N; i += blockDim.x) {
@@ -341,9 +222,10 @@ int plk_trim_launch(const uint8_t* d, uint64_t len, uint32_t* d_nz, hipStream_t 
 }
 
 // Direct convolution when one operand is short: out[i] = sum_j a[j] b[i-j] mod 17 over the
-// short operand s (length ls <= 32, staged in LDS), the long one read coalesced.
+// short operand s (length ls <= 32, staged in LDS), the long one read coalesced.  (The trimmed
+// length is trim_kernel's.)
 __global__ __launch_bounds__(256) void polymul_direct_kernel(const uint8_t* lg, uint64_t llg, const uint8_t* sh,
-                                                             int lsh, uint8_t* out8, uint32_t* nz) {
+                                                             int lsh, uint8_t* out8) {
   __shared__ uint32_t S[64];
   if ((int)threadIdx.x < lsh) S[threadIdx.x] = sh[threadIdx.x] % 17u;
   __syncthreads();
@@ -356,7 +238,6 @@ __global__ __launch_bounds__(256) void polymul_direct_kernel(const uint8_t* lg, 
     }
     out8[i] = (uint8_t)(acc % 17u);
   }
-  (void)nz;   // trimmed length: trim_kernel
 }
 
 // ------------------------------------------------------------------------------ host side
@@ -419,13 +300,10 @@ int plk_ntt_init_tables(void) {
   TwHost& T = g_tw[dev].bb;
   TwHost& T29 = g_tw[dev].f29;
   if (T.d_small_f) return PLK_OK;
-  // tiles of 2^12 rows with two arrays exceed the default 64 KB dynamic-LDS limit
+  // two arrays of 2^12 words and two stage tables exceed the default 64 KB dynamic-LDS limit
+  // (ntt_pass_kernel's one array and one table, 33 KB, do not)
   const int lds_max = 150 * 1024;   // leaves room for the kernels' static LDS
   PLK_HIP(hipFuncSetAttribute((const void*)polymul_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-  PLK_HIP(hipFuncSetAttribute((const void*)ntt_pass_kernel<false, IN_U32, OUT_U32>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-  PLK_HIP(hipFuncSetAttribute((const void*)ntt_pass_kernel<true, IN_U32, OUT_U32>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
   const uint32_t w27 = bb::hpow(bb::GENERATOR, (bb::P - 1) >> bb::TWO_ADICITY);   // order 2^27
   const uint32_t w27i = bb::hpow(w27, bb::P - 2);
   const int SM = 1 << PLK_NTT_SMALL_LOG;
@@ -609,10 +487,8 @@ size_t plk_poly_mul_workspace_bytes(uint64_t la, uint64_t lb) {
   return (size_t)2 * 4 * (1ull << k);
 }
 
-static size_t pass_lds(int M, int C, bool center) {
-  const size_t rows = 1u << M;
-  return (center ? 2 : 1) * C * (size_t)col_stride((int)rows) * 4 + (center ? 2 : 1) * rows * 4 + (size_t)C * M * 4;
-}
+// dynamic LDS of ntt_pass_kernel: the padded array and the stage table
+static size_t pass_lds(int k) { return ((size_t)col_stride(1 << k) + ((size_t)1 << k)) * 4; }
 
 // m products of one transform size 2^k through the wave engine (workspace 2^(k+3) bytes each);
 // es[i] > 0: a wrapped product (product_plan) with es[i] top coefficients.
@@ -791,7 +667,7 @@ int plk_poly_mul_launch(const uint8_t* d_a, uint64_t la, const uint8_t* d_b, uin
     const uint64_t blocks64 = (rl + 255) / 256;
     const int blocks = (int)(blocks64 > 8192 ? 8192 : blocks64);
     hipLaunchKernelGGL(polymul_direct_kernel, dim3(blocks), dim3(256), 0, st, lg, la >= lb ? la : lb, sh, (int)mn,
-                       d_out, d_nz);
+                       d_out);
     PLK_HIP(hipGetLastError());
     if (d_nz) hipLaunchKernelGGL(trim_kernel, dim3(1), dim3(1024), 0, st, d_out, rl, d_nz);
     PLK_HIP(hipGetLastError());
@@ -948,18 +824,13 @@ int plk_ntt_launch(uint32_t* d, int k, int batch, int inverse, hipStream_t st) {
     return PLK_ERR_RANGE;
   }
   if (plk_wave_ntt_supported(k)) return plk_wave_ntt_launch(d, k, batch, inverse, 0, st);
-  // k <= 12: one workgroup-tile pass (lo = 0, a single tile holds the whole array)
-  const Tw tw = inverse ? tw_inv() : tw_fwd();
-  const Pass p{k, 0, k, 1};
-  const size_t lds = pass_lds(p.M, p.C, false);
+  // k <= 12: one workgroup per array
+  const uint32_t* small = inverse ? tw_inv().small : tw_fwd().small;
+  const size_t lds = pass_lds(k);
   for (int b = 0; b < batch; b++) {
     uint32_t* db = d + ((uint64_t)b << k);
-    if (inverse)
-      hipLaunchKernelGGL((ntt_pass_kernel<true, IN_U32, OUT_U32>), dim3(1, 1), dim3(NTT_THREADS), lds, st, p, db, db,
-                         nullptr, nullptr, 0, 0, tw, nullptr, 0, 0u, nullptr);
-    else
-      hipLaunchKernelGGL((ntt_pass_kernel<false, IN_U32, OUT_U32>), dim3(1, 1), dim3(NTT_THREADS), lds, st, p, db, db,
-                         nullptr, nullptr, 0, 0, tw, nullptr, 0, 0u, nullptr);
+    if (inverse) hipLaunchKernelGGL(ntt_pass_kernel<true>, dim3(1), dim3(NTT_THREADS), lds, st, k, db, small);
+    else hipLaunchKernelGGL(ntt_pass_kernel<false>, dim3(1), dim3(NTT_THREADS), lds, st, k, db, small);
   }
   PLK_HIP(hipGetLastError());
   return PLK_OK;

@@ -36,129 +36,23 @@
 #include <type_traits>
 #include <vector>
 
-#ifndef PLK_NTT_DIAG
-#define PLK_NTT_DIAG 0        // tuning builds only: bit 0 skips the butterflies, bit 1 the LDS exchanges,
-                              // bit 2 makes them lane-linear (conflict-free, wrong data), bit 3 loads
-                              // one input byte per thread instead of E, bit 4 skips the column-table loads
-#endif
-
 namespace {
 
-#ifndef PLK_NTT_R12
-#define PLK_NTT_R12 2          // register bits per thread for 2^12 tiles (1024 threads)
-#endif
-#ifndef PLK_NTT_R13
-#define PLK_NTT_R13 3          // ... for 2^13 tiles
-#endif
-#ifndef PLK_NTT_RC13
-#define PLK_NTT_RC13 3         // register bits per thread of the 2^13-tile center kernel
-#endif
-#ifndef PLK_NTT_BYTE_LUT
-#define PLK_NTT_BYTE_LUT 1     // byte values through a 256-entry LDS table (0: arithmetic in registers)
-#endif
-#ifndef PLK_NTT_SWZ
-#define PLK_NTT_SWZ 1          // XOR-swizzled (bank-conflict-free) exchange layout; 0: the 1-in-32 pad
-#endif
-#ifndef PLK_NTT_CENTER_SWZ
-// center exchanges: 3 = the padded layout with barriers only where a wave's element set changes
-// (Eng::same_sets; round 5: 2^13 centre 80.2 -> 71.3-72.3 us per launch, prove median 0.394-0.407 ->
-// 0.377-0.391 ms, alternating on one box), 0 = padded with a barrier after every exchange's writes
-// and reads, 1 / 2 = swizzled everywhere / where the padding conflicts (measured equal to 0)
-#define PLK_NTT_CENTER_SWZ 3
-#endif
-#ifndef PLK_NTT_CENTER_SWZ12
-// ... the same for the 2^12-tile center: 4 = one pass-wide conflict-free swizzle with the set-based
-// barriers (round 5: poly_mul 2^19 x 2^19 24.14-24.42 -> 23.73-24.07 us alternating; 1 = swizzled
-// per exchange, double-buffered, with PLK_NTT_RC12 = 3: 25.2 -> 23.7 us)
-#define PLK_NTT_CENTER_SWZ12 4
-#endif
-#ifndef PLK_NTT_DBUF13
-// 2^13-tile high passes: two exchange buffers, one barrier per exchange (round 5: prover forward
-// passes 46.8 / 39.2 -> 45.2 / 38.4 us, inverse M = 8 31.1 -> 30.4 us, prove median -0.5..1 %)
-#define PLK_NTT_DBUF13 1
-#endif
-#ifndef PLK_NTT_CENTER_PW
-// F29 centres' twiddles as {w, p - w} pairs (no subtraction in the forward DIF): bit 0 = 2^12 tiles
-// (round 5: poly_mul 2^19 x 2^19 23.62-23.72 -> 23.34-23.48 us, three alternations), bit 1 = 2^13
-// tiles with 2^11 pairs (spills 24-32 B/lane at its 64-VGPR budget: prove median 0.383-0.390 ->
-// 0.405-0.417 ms -- off)
-#define PLK_NTT_CENTER_PW 1
-#endif
-#ifndef PLK_NTT_CENTER12_2BUF
-#define PLK_NTT_CENTER12_2BUF 0   // the 2^12 centre's b pass in its own buffer (no barrier between a's and b's passes)
-#endif
-#ifndef PLK_NTT_TRIBUF
-#define PLK_NTT_TRIBUF 0       // swizzled double-buffered passes: a third buffer lets wave-local exchanges skip their barrier
-#endif
-#ifndef PLK_NTT_ALT_ARRAYS
-// pass kernels: exchange buffers alternate across a block's arrays, no barrier between arrays (round 5:
-// prove median 0.373-0.397 vs 0.377-0.387 ms, four alternations -- off)
-#define PLK_NTT_ALT_ARRAYS 0
-#endif
-#ifndef PLK_NTT_LO_USWZ
-// standalone lo = 0 passes: the pass-wide swizzle with set-based barriers (Eng SWZ 4; round 5: 2^20
-// forward F29 13.1-13.3 -> 12.5-12.55 us, BabyBear 13.5 -> 12.85-12.9 us, three alternations)
-#define PLK_NTT_LO_USWZ 1
-#endif
-#ifndef PLK_NTT_WRAP_INLINE
-#define PLK_NTT_WRAP_INLINE 1  // wrapped tops fixed at the end of the last inverse pass (0: wrap_fix_kernel launches)
-#endif
-#ifndef PLK_NTT_CW13
-#define PLK_NTT_CW13 8         // min waves per SIMD (launch bound): 8 = two 1024-thread blocks per CU
-#endif
-#ifndef PLK_NTT_CENTER_PF
-#define PLK_NTT_CENTER_PF 0    // center: the next item's A loaded during the current item's inverse rounds
-#endif
-// Round-4 latency-hiding variants, per-kernel times from one box (tools/ab_kernels.sh, prover 2^20,
-// forward M = 8 / forward M = 9 / inverse M = 8 passes, us): all off 46.9 / 39.4 / 30.9;
-// PREFETCH + XCH_REMAT 45.2 / 38.6 / 31.7 (the inverse passes' prefetch: +0.8, so off there);
-// U8_KRSRC alone 50.5 / 43.3 / 30.5 (slower); PREFETCH alone spilled (41.8 us inverse).
-#ifndef PLK_NTT_PREFETCH
-#define PLK_NTT_PREFETCH 1     // forward pass kernels load array i+1 before array i's butterflies
-#endif
-#ifndef PLK_NTT_PREFETCH_INV
-#define PLK_NTT_PREFETCH_INV 0 // ... and the inverse ones job i+1 before job i's
-#endif
-#ifndef PLK_NTT_XCH_REMAT
-#define PLK_NTT_XCH_REMAT 1    // swizzled exchange addresses recomputed per pass, not held across the array loop
-#endif
-#ifndef PLK_NTT_M17
-#define PLK_NTT_M17 1          // COLT byte outputs: 1 = mod 17 of the index through an LDS table, 0 = 24-bit arithmetic
-#endif
-#ifndef PLK_NTT_FIX_FILL
-#define PLK_NTT_FIX_FILL 0     // the shared-operand lo = 0 launch fills its last round of blocks with operands used once
-#endif
-#ifndef PLK_NTT_COLI_DERIVE
-#define PLK_NTT_COLI_DERIVE 1  // last inverse passes: scaled column factors from the lo / hi roots by products (0: the table)
-#endif
-#ifndef PLK_NTT_DERIVE
-#define PLK_NTT_DERIVE 1       // 2^13-tile first forward passes compute a derived operand (WArrs::derive); 0: compiled out
-#endif
-#ifndef PLK_NTT_U8_KRSRC
-#define PLK_NTT_U8_KRSRC 0     // byte loads: one buffer resource per register index (one offset VGPR)
-#endif
-#ifndef PLK_NTT_RC12
-// register bits per thread of the 2^12-tile center kernel: 3 = 512 threads of 8 elements, 4 rounds of
-// 3 stages per transform (3 exchanges instead of 5); with the swizzled exchanges poly_mul 2^19 x 2^19
-// 24.95-25.44 -> 23.55-23.85 us (same box, alternating, tools/c3_lib_ab.sh; 2 = 1024 threads)
-#define PLK_NTT_RC12 3
-#endif
-constexpr int wt_rc(int TB) { return TB == 13 ? PLK_NTT_RC13 : PLK_NTT_RC12; }
+// Tile shapes (the measurements that chose them: DESIGN.md section 4).
+// register bits per thread of the center kernels (wt_center_kernel, wt_fixfwd_kernel), both tile
+// sizes: 2^12 tiles run 512 threads of 8 elements, 4 rounds of 3 stages per transform
+constexpr int wt_rc(int) { return 3; }
 constexpr int wt_ntc(int TB) { return 1 << (TB - wt_rc(TB)); }
-// register bits per thread for a tile size; the block has 2^(TB-R) threads
-constexpr int wt_r(int TB) { return TB == 13 ? PLK_NTT_R13 : PLK_NTT_R12; }
+// register bits per thread of the pass kernels; the block has 2^(TB-R) = 1024 threads
+constexpr int wt_r(int TB) { return TB == 13 ? 3 : 2; }
 constexpr int wt_nt(int TB) { return 1 << (TB - wt_r(TB)); }
+// the 2^13 centre's launch bound, waves per SIMD: 8 = two 1024-thread blocks per CU
+constexpr int WT_CENTER13_WAVES = 8;
 constexpr int WT_MAX_HI12 = 8;                 // widest high-bit pass with 2^12 tiles
 constexpr int WT_MAX_HI13 = 10;                // ... with 2^13 tiles
 constexpr uint32_t M17_LUT = 1040;             // mod-17 table of the byte outputs (F::out17_idx < 1035)
 
 __device__ __forceinline__ int wphys(int e) { return e + (e >> 5); }
-// x mod 17 for x < M17_LUT with full-rate 24-bit multiplies: floor(x / 17) = (241 x) >> 12 there
-// (checked for every x < 1040), then x - 17 q as one v_mad_i32_i24
-__device__ __forceinline__ uint32_t mod17_small(uint32_t x) {
-  const uint32_t q = __umul24(x, 241u) >> 12;
-  return (uint32_t)(__mul24((int)q, -17) + (int)x);
-}
 
 // A tile's words (or bytes) through a buffer resource on its uniform base: every access is one
 // 32-bit VGPR offset against scalar registers (no 64-bit address per element; offsets stay below
@@ -187,6 +81,11 @@ struct TileBuf {
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v, r, off, 0, 0);
   }
 };
+
+// how a pass's rounds exchange their registers through LDS (Eng::exchange)
+enum XLayout { X_SWZ_EACH, X_PAD, X_SWZ_PASS };
+// the centre kernels' layout: the pass-wide swizzle for 2^12 tiles, the padded layout for 2^13
+constexpr XLayout wt_center_layout(int TB) { return TB == 13 ? X_PAD : X_SWZ_PASS; }
 
 struct WPass {
   int k;    // log2 N
@@ -277,10 +176,9 @@ struct FBB {
   // pointwise product's R^-1 is folded into the final scale, see ntt_group)
   __device__ static __forceinline__ uint32_t byte_val(uint32_t b) { return b % 17u; }
   __device__ static __forceinline__ uint32_t out17(uint32_t v, uint32_t ninv) { return bb::mmul(v, ninv) % 17u; }
-  // the same when the scale is already applied (the inverse column table holds it)
-  __device__ static __forceinline__ uint32_t out17s(uint32_t v) { return v % 17u; }
-  // an index < M17_LUT whose entry of the mod-17 table is out17s(v): 2^8 = 1 (mod 17), so a word is
-  // congruent to the sum of its bytes (one v_dot4_u32_u8)
+  // the same when the scale is already applied (the scaled column factors hold it), as an index
+  // < M17_LUT into the mod-17 table: 2^8 = 1 (mod 17), so a word is congruent to the sum of its
+  // bytes (one v_dot4_u32_u8)
   __device__ static __forceinline__ uint32_t out17_idx(uint32_t v) { return __builtin_amdgcn_udot4(v, 0x01010101u, 0u, false); }
   __device__ static __forceinline__ uint32_t scale(uint32_t c, uint32_t ninv) { return bb::mmul(c, ninv); }
   __device__ static __forceinline__ uint32_t canon(uint32_t v) { return v; }   // always reduced
@@ -363,20 +261,15 @@ struct F29 {
     constexpr uint32_t C = (17u << 25) - f29::P;
     return (y + (y > (f29::P - 1) / 2 ? C : 0u)) % 17u;
   }
-  // the same when the scale is already applied (the inverse column table holds it): y < 8p, one
+  // the same when the scale is already applied (the scaled column factors hold it): y < 8p, one
   // reduction to y < 4p; the centered value is c = y - j p with j = floor((y + (p - 1) / 2) / p)
-  // (a multiply-high: exact below 6p - 1), and p = 12 mod 17, so c = y + 5 j mod 17
-  __device__ static __forceinline__ uint32_t out17s(uint32_t v) {
-    const uint32_t y = red4(v);
-    const uint32_t j = __umulhi(y + (f29::P - 1) / 2, 2454267022u) >> 28;   // ceil(2^60 / p)
-    return (y + 5u * j) % 17u;
-  }
-  // the same as an index into a mod-17 table (< M17_LUT): y is congruent to the sum of its bytes
+  // (a multiply-high: exact below 6p - 1), and p = 12 mod 17, so c = y + 5 j mod 17.  Returned as
+  // an index into the mod-17 table (< M17_LUT): y is congruent to the sum of its bytes
   // (2^8 = 1 mod 17), so the centered value is congruent to bytesum(y) + 5 j <= 4 * 255 + 5 * 3
   // (one v_dot4_u32_u8 and a v_mad_u32_u24 instead of the % 17: 3 VALU fewer per output byte)
   __device__ static __forceinline__ uint32_t out17_idx(uint32_t v) {
     const uint32_t y = red4(v);
-    const uint32_t j = __umulhi(y + (f29::P - 1) / 2, 2454267022u) >> 28;
+    const uint32_t j = __umulhi(y + (f29::P - 1) / 2, 2454267022u) >> 28;   // ceil(2^60 / p)
     return __builtin_amdgcn_udot4(y, 0x01010101u, 5u * j, false);
   }
   __device__ static __forceinline__ uint32_t scale(uint32_t c, uint32_t ninv) { return f29::red1(f29::mmul(c, ninv)); }
@@ -384,8 +277,7 @@ struct F29 {
 
 // Tile engine: TB tile bits, R local bits per thread (E = 2^R registers, 2^(TB-R) threads
 // per tile), a pass of M row bits.  HIGH = the pass is over high index bits (lo > 0):
-// exactly the passes with M < TB.  Tiles of 2^12 use double-buffered exchanges (one barrier
-// each); 2^13 tiles a single buffer (two barriers) so two blocks fit a CU's LDS.
+// exactly the passes with M < TB.
 template <int TB, int R, int M, class F = FBB>
 struct Eng {
   static constexpr int E = 1 << R;
@@ -393,12 +285,13 @@ struct Eng {
   static constexpr bool HIGH = M < TB;
   static constexpr int NR = (M + R - 1) / R;   // rounds
   static constexpr int BUF = (1 << TB) + (1 << TB) / 32;   // padded exchange buffer (words)
-  // double-buffered exchanges (one barrier each): 2^12 tiles, and the high passes of 2^13 tiles
-  // with PLK_NTT_DBUF13 (2 x 33 KB + their small tables: still two blocks per CU; the lo = 0
-  // kernels keep one buffer beside their 2^13-word twiddle table)
-  static constexpr bool DBUF = TB <= 12 || (PLK_NTT_DBUF13 && M < TB);
+  // two exchange buffers in the pass kernels (nbuf): every high pass alternates between them, one
+  // barrier per exchange (2 x 33 KB + the small tables still leave two 2^13-tile blocks per CU).
+  // The 2^13-tile lo = 0 pass kernels keep one buffer beside their 2^13-word twiddle table.  The
+  // 2^12-tile lo = 0 pass kernels reserve two and use the first (X_SWZ_PASS needs one): their LDS
+  // size is left as it was.
+  static constexpr bool DBUF = TB <= 12 || M < TB;
   static constexpr int XCH = NR - 1;            // exchanges per pass
-  static constexpr int NBUF = XCH == 0 ? 0 : (XCH > 1 && DBUF ? 2 : 1);
 
   // DIF rounds take chunks of <= R stage bits from the top (the short chunk last), DIT rounds
   // from the bottom with the short chunk FIRST: either way the first and last rounds of a pass
@@ -430,12 +323,9 @@ struct Eng {
   // the radix-2 stages of round Q, in registers.  Stage 0 has twiddle 1: DIT always skips the
   // multiply there (its x inputs are < 2p, F::dit1), DIF when TRIV0 (a forward pass whose
   // outputs go to the column multiply or the canonical store, F::dif1).  PW: the table holds
-  // {w, p - w} pairs (F29 DIF without the subtraction).
-  // PWB (the centre's mixed table, PW false): stages s < PWB read {w, p - w} pairs at uint2 index
-  // 2^s + r, the others single words at 2^s + r + 2^PWB (0: single words everywhere)
-  template <int Q, bool INV, bool PW = false, bool TRIV0 = false, int PWB = 0>
+  // {w, p - w} pairs (F29 DIF without the subtraction; a DIT over the same table reads w).
+  template <int Q, bool INV, bool PW = false, bool TRIV0 = false>
   __device__ static __forceinline__ void round(uint32_t (&v)[E], uint32_t b, const uint32_t* Tsm) {
-    if (PLK_NTT_DIAG & 1) return;
     constexpr int LB = lbq(Q, INV), SL = s_lo(Q, INV), SH = s_hi(Q, INV);
     const uint32_t blow = b & ((1u << LB) - 1);
 #pragma unroll
@@ -462,16 +352,11 @@ struct Eng {
         }
         if constexpr (PW) {
           const uint2 wp = reinterpret_cast<const uint2*>(Tsm)[(1u << s) + rr];
-          F::difp(v[k], v[k | (1 << q)], wp.x, wp.y, red);
-          continue;
-        }
-        if (s < PWB) {   // (compile-time after unrolling)
-          const uint2 wp = reinterpret_cast<const uint2*>(Tsm)[(1u << s) + rr];
           if (!INV) F::difp(v[k], v[k | (1 << q)], wp.x, wp.y, red);
           else F::dit(v[k], v[k | (1 << q)], wp.x, red);
           continue;
         }
-        const uint32_t w = Tsm[(1u << s) + rr + (PWB ? (1u << PWB) : 0u)];
+        const uint32_t w = Tsm[(1u << s) + rr];
         if (!INV) F::dif(v[k], v[k | (1 << q)], w, red);
         else F::dit(v[k], v[k | (1 << q)], w, red);
       }
@@ -562,22 +447,6 @@ struct Eng {
     }
     return true;
   }
-  // the padded layout (word e + e / 32) is conflict-free for exchange q when the 32 lanes of a
-  // half-wave hit 32 distinct banks in both the writing and the reading round
-  static constexpr bool pad_ok(int q, bool inv) {
-    for (int t = 0; t < 2; t++) {
-      bool used[32] = {};
-      for (uint32_t l = 0; l < 32; l++) {
-        uint32_t e = 0;
-        for (int i = 0; i < 5; i++)
-          if ((l >> i) & 1) e |= 1u << lane_bit(q + t, inv, i);
-        const uint32_t bank = (e + (e >> 5)) & 31u;
-        if (used[bank]) return false;
-        used[bank] = true;
-      }
-    }
-    return true;
-  }
   template <int Q, bool INV>
   __device__ static __forceinline__ uint32_t swz_h(uint32_t e) {
     constexpr Swz s = swz(Q, INV);
@@ -588,13 +457,10 @@ struct Eng {
     return h;
   }
 
-  // registers (mapping from) -> LDS -> registers (mapping to).  Double-buffered: one barrier
-  // suffices (the buffer written next was last read before the previous barrier); single
-  // buffer: a second barrier before the buffer is written again.
-  // Barriers an exchange needs (round 5).  A round's mapping gives every wave a SET of elements,
-  // fixed by the element bits its thread-id bits >= 6 (the wave id) select.  Exchange q writes the
-  // wave's round-q set and reads its round-(q + 1) set; with ONE layout for every exchange of a
-  // kernel (the padded one, SWZ = 3) two waves' accesses can only meet on a word when their sets
+  // Barriers an exchange needs when ONE layout serves every exchange of a kernel (X_PAD and
+  // X_SWZ_PASS below).  A round's mapping gives every wave a SET of elements, fixed by the element
+  // bits its thread-id bits >= 6 (the wave id) select.  Exchange q writes the wave's round-q set
+  // and reads its round-(q + 1) set; two waves' accesses can only meet on a word when their sets
   // differ, so:
   //   * a wave's reads of exchange q and another wave's writes of exchange q + 1 are both of round
   //     q + 1's sets -- disjoint -- so no barrier trails an exchange and one buffer suffices;
@@ -608,7 +474,7 @@ struct Eng {
     return true;
   }
   static constexpr bool wave_local(int q, bool inv) { return same_sets(q, inv, q + 1, inv); }
-  // One XOR swizzle for EVERY round of a lo = 0 pass in both directions (SWZ = 4): masks m[j] for
+  // One XOR swizzle for EVERY round of a lo = 0 pass in both directions (X_SWZ_PASS): masks m[j] for
   // the element bits j >= 5 that some round puts on a half-wave's 32 lanes, found by depth-first
   // search so that each round's 5 lane vectors are independent (conflict-free); with one layout the
   // barrier rules above hold.  (TB 12 / R 3 and TB 13 / R 3 have one; uswz_ok says so.)
@@ -661,21 +527,8 @@ struct Eng {
       if (s.m[j]) h ^= ((e >> j) & 1u) ? s.m[j] : 0u;
     return h;
   }
-  // Three exchange buffers rotating (PLK_NTT_TRIBUF, swizzled double-buffered passes): a wave-local
-  // exchange then needs no barrier -- its words are its own wave's, and the block exchanges on
-  // either side (the reads of the one before, the writes of the one after, which can run beside it
-  // in other waves) use the other two buffers.  Only where no two wave-local exchanges follow each
-  // other (longer runs would need more buffers): the 2^12-tile high passes of 7-8 bits.
-  static constexpr int wl_run(bool inv) {
-    int mx = 0, run = 0;
-    for (int q = 0; q + 1 < NR; q++) {
-      run = wave_local(q, inv) ? run + 1 : 0;
-      mx = run > mx ? run : mx;
-    }
-    return mx;
-  }
-  static constexpr bool tri(bool inv) { return PLK_NTT_TRIBUF && DBUF && wl_run(inv) == 1; }
-  static constexpr int nbuf() { return XCH == 0 ? 1 : (tri(false) || tri(true) ? 3 : (NBUF ? NBUF : 1)); }
+  // exchange buffers of a pass kernel
+  static constexpr int nbuf() { return XCH > 1 && DBUF ? 2 : 1; }
   // the wave's own LDS writes before its reads of other lanes' words (rocPRIM's wave_barrier)
   __device__ static __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -683,108 +536,68 @@ struct Eng {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
 
-  // SWZ: 0 = the padded layout, 1 = the swizzled layout wherever it is conflict-free, 2 = the
-  // swizzled layout only where the padded one conflicts (fewer live address registers: the center),
-  // 3 = the padded layout with only the barriers above (one buffer), 4 = the same with the
-  // pass-wide swizzle uswz (conflict-free)
-  template <int Q, bool INV, int SWZ>
+  // Exchange layouts (XLayout):
+  //   X_SWZ_EACH  high passes: a swizzle chosen per exchange (swz), two buffers taken in turn, one
+  //               block barrier per exchange (the buffer written next was last read before the
+  //               previous barrier)
+  //   X_PAD       the 2^13 centre: the 1-in-32 padded layout, one buffer, the set-based barriers above
+  //   X_SWZ_PASS  lo = 0 passes and the 2^12 centre: the pass-wide swizzle (uswz), one buffer, the
+  //               set-based barriers above
+  template <int Q, bool INV, XLayout L>
+  __device__ static __forceinline__ uint32_t xch_h(uint32_t e) {
+    if constexpr (L == X_SWZ_PASS) return uswz_h(e);
+    else return swz_h<Q, INV>(e);
+  }
+  // registers (mapping from) -> LDS -> registers (mapping to)
+  template <int Q, bool INV, XLayout L>
   __device__ static __forceinline__ void exchange(uint32_t (&v)[E], uint32_t* buf, uint32_t bf, int lbf, uint32_t bt,
                                                   int lbt) {
-    if (PLK_NTT_DIAG & 2) return;
-    if constexpr (SWZ == 4) {
-      static_assert(uswz_ok(), "no pass-wide conflict-free swizzle for this tile shape");
-      uint32_t xw4 = (bf ^ uswz_h(bf)) << 2, xr4 = (bt ^ uswz_h(bt)) << 2;
-      if (PLK_NTT_XCH_REMAT) {
-        asm volatile("" : "+v"(xw4));
-        asm volatile("" : "+v"(xr4));
-      }
-      char* bb = reinterpret_cast<char*>(buf);
-#pragma unroll
-      for (int k = 0; k < E; k++) {
-        const uint32_t ek = (uint32_t)k << lbf;
-        const uint32_t lo = ((ek & 31u) ^ uswz_h(ek)) << 2, hi = (ek & ~31u) << 2;
-        *reinterpret_cast<uint32_t*>(bb + (lo ? (xw4 ^ lo) : xw4) + hi) = v[k];
-      }
-      if constexpr (wave_local(Q, INV)) wave_sync();
-      else __syncthreads();
-#pragma unroll
-      for (int k = 0; k < E; k++) {
-        const uint32_t ek = (uint32_t)k << lbt;
-        const uint32_t lo = ((ek & 31u) ^ uswz_h(ek)) << 2, hi = (ek & ~31u) << 2;
-        v[k] = *reinterpret_cast<const uint32_t*>(bb + (lo ? (xr4 ^ lo) : xr4) + hi);
-      }
-      return;
-    }
-    if constexpr (SWZ == 3) {
+    if constexpr (L == X_PAD) {
 #pragma unroll
       for (int k = 0; k < E; k++) buf[wphys((int)(bf + ((uint32_t)k << lbf)))] = v[k];
       if constexpr (wave_local(Q, INV)) wave_sync();
       else __syncthreads();
 #pragma unroll
       for (int k = 0; k < E; k++) v[k] = buf[wphys((int)(bt + ((uint32_t)k << lbt)))];
-      return;
-    }
-    if (PLK_NTT_SWZ && SWZ && swz_ok(Q, INV) && (SWZ == 1 || !pad_ok(Q, INV))) {
+    } else {
+      static_assert(L == X_SWZ_PASS ? uswz_ok() : swz_ok(Q, INV), "no conflict-free swizzle for this exchange");
       // e = base | k << lb (disjoint bits) and h is linear: h(e) = h(base) ^ h(k << lb).  h only
       // moves bits < 5 and the bits >= 5 of k << lb are disjoint from base's, so the word is
       // (xw ^ lo_k) + hi_k: one XOR with a constant (none when lo_k = 0) and the rest in the
       // ds_write / ds_read offset, on byte addresses (no per-element shift)
-      uint32_t xw4 = (bf ^ swz_h<Q, INV>(bf)) << 2, xr4 = (bt ^ swz_h<Q, INV>(bt)) << 2;
-      if (PLK_NTT_XCH_REMAT) {
-        // opaque here: the per-register addresses (xw4 ^ lo) are formed at each use -- one XOR
-        // each -- instead of ~7 registers per base live across a kernel's whole array loop
-        asm volatile("" : "+v"(xw4));
-        asm volatile("" : "+v"(xr4));
-      }
+      uint32_t xw4 = (bf ^ xch_h<Q, INV, L>(bf)) << 2, xr4 = (bt ^ xch_h<Q, INV, L>(bt)) << 2;
+      // opaque here: the per-register addresses (xw4 ^ lo) are formed at each use -- one XOR
+      // each -- instead of ~7 registers per base live across a kernel's whole array loop
+      asm volatile("" : "+v"(xw4));
+      asm volatile("" : "+v"(xr4));
       char* bb = reinterpret_cast<char*>(buf);
 #pragma unroll
       for (int k = 0; k < E; k++) {
         const uint32_t ek = (uint32_t)k << lbf;
-        const uint32_t lo = ((ek & 31u) ^ swz_h<Q, INV>(ek)) << 2, hi = (ek & ~31u) << 2;
+        const uint32_t lo = ((ek & 31u) ^ xch_h<Q, INV, L>(ek)) << 2, hi = (ek & ~31u) << 2;
         *reinterpret_cast<uint32_t*>(bb + (lo ? (xw4 ^ lo) : xw4) + hi) = v[k];
       }
-      if constexpr (tri(INV) && wave_local(Q, INV)) wave_sync();
+      if constexpr (L == X_SWZ_PASS && wave_local(Q, INV)) wave_sync();
       else __syncthreads();
 #pragma unroll
       for (int k = 0; k < E; k++) {
         const uint32_t ek = (uint32_t)k << lbt;
-        const uint32_t lo = ((ek & 31u) ^ swz_h<Q, INV>(ek)) << 2, hi = (ek & ~31u) << 2;
+        const uint32_t lo = ((ek & 31u) ^ xch_h<Q, INV, L>(ek)) << 2, hi = (ek & ~31u) << 2;
         v[k] = *reinterpret_cast<const uint32_t*>(bb + (lo ? (xr4 ^ lo) : xr4) + hi);
       }
-      if (!DBUF) __syncthreads();
-      return;
     }
-    if (PLK_NTT_DIAG & 4) {   // timing only: conflict-free lane-linear exchange (wrong data)
-#pragma unroll
-      for (int k = 0; k < E; k++) buf[k * NT + threadIdx.x] = v[k];
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < E; k++) v[k] = buf[k * NT + (threadIdx.x ^ 1)];
-      if (!DBUF) __syncthreads();
-      return;
-    }
-#pragma unroll
-    for (int k = 0; k < E; k++) buf[wphys((int)(bf + ((uint32_t)k << lbf)))] = v[k];
-    if constexpr (tri(INV) && wave_local(Q, INV) && SWZ < 3) wave_sync();
-    else __syncthreads();
-#pragma unroll
-    for (int k = 0; k < E; k++) v[k] = buf[wphys((int)(bt + ((uint32_t)k << lbt)))];
-    if (!DBUF) __syncthreads();
   }
 
   // rounds Q .. NR-1 of a pass; registers hold the mapping of round Q on entry and of the
-  // last round on exit.  xc selects the exchange buffer (it counts exchanges).
-  // SWZ: the swizzled exchange layout where it is conflict-free (the center kernel passes false:
-  // it has no VGPRs to spare for the two extra base registers)
-  template <bool INV, int SWZ = 1, bool PW = false, bool TRIV0 = false, int PWB = 0, int Q = 0>
-  __device__ static __forceinline__ void pass(uint32_t (&v)[E], uint32_t tid, uint32_t* bufs, int xc,
-                                              const uint32_t* Tsm) {
-    round<Q, INV, PW, TRIV0, PWB>(v, base_q<Q>(tid, INV), Tsm);
+  // last round on exit
+  template <bool INV, XLayout L, bool PW = false, bool TRIV0 = false, int Q = 0>
+  __device__ static __forceinline__ void pass(uint32_t (&v)[E], uint32_t tid, uint32_t* bufs, const uint32_t* Tsm) {
+    round<Q, INV, PW, TRIV0>(v, base_q<Q>(tid, INV), Tsm);
     if constexpr (Q + 1 < NR) {
-      exchange<Q, INV, SWZ>(v, bufs + (!DBUF || SWZ >= 3 ? 0 : (tri(INV) ? ((xc + Q) % 3) : ((xc + Q) & 1)) * BUF),
-                            base_q<Q>(tid, INV), lbq(Q, INV),
-                            base_q<Q + 1>(tid, INV), lbq(Q + 1, INV));
-      pass<INV, SWZ, PW, TRIV0, PWB, Q + 1>(v, tid, bufs, xc, Tsm);
+      static_assert(L != X_SWZ_EACH || DBUF, "per-exchange swizzles alternate between two buffers");
+      exchange<Q, INV, L>(v, bufs + (L == X_SWZ_EACH ? (Q & 1) * BUF : 0), base_q<Q>(tid, INV), lbq(Q, INV),
+                          base_q<Q + 1>(tid, INV), lbq(Q + 1, INV));
+      pass<INV, L, PW, TRIV0, Q + 1>(v, tid, bufs, Tsm);
     }
   }
 
@@ -868,23 +681,7 @@ __device__ __forceinline__ void load_pass_tw(uint32_t* Tsm, const uint32_t* smal
   }
 }
 
-// the centre's mixed table (Eng::round's PWB): {w, p - w} pairs for the first 2^PWB entries, the
-// others as single words at their index + 2^PWB (2^TB + 2^PWB words)
-template <int TB, int PWB, int NT>
-__device__ __forceinline__ void load_center_tw(uint32_t* T, const uint32_t* small) {
-  const TileBuf bs(small);
-#pragma unroll
-  for (int i = 0; i < ((1 << TB) + NT - 1) / NT; i++) {
-    const int j = i * NT + (int)threadIdx.x;
-    if (j < (1 << TB)) {
-      const uint32_t w = bs.ld((uint32_t)j);
-      if (j < (1 << PWB)) reinterpret_cast<uint2*>(T)[j] = make_uint2(w, f29::P - w);
-      else T[j + (1 << PWB)] = w;
-    }
-  }
-}
-
-// the same as {w, p - w} pairs (F29 forward passes)
+// the same as {w, p - w} pairs (F29 forward passes and the 2^12 centre)
 template <int M, int NT>
 __device__ __forceinline__ void load_pass_tw_pairs(uint32_t* Tsm, const uint32_t* small) {
 #pragma unroll
@@ -964,26 +761,9 @@ __global__ __launch_bounds__(wt_nt(TB), TB == 13 && M == TB ? 4 : 8) void wt_fwd
     if constexpr (FROM_U8) {
       const uint64_t ls = ar.ls;
       const uint32_t lim = ls > tb ? (uint32_t)(ls - tb < 0xFFFFFFFFull ? ls - tb : 0xFFFFFFFFull) : 0u;
-      if constexpr (PLK_NTT_U8_KRSRC && !(PLK_NTT_DIAG & 8) && G::template ksplit<0, false>()) {
-        // register index k reads byte o0 + kpart(k): its own resource based at kpart(k) with the
-        // range shortened by as much, so one offset VGPR serves all E loads and the range check
-        // still zero-pads past the operand
-#pragma unroll
-        for (int k = 0; k < G::E; k++) {
-          const uint32_t kp = G::template kpart<0, false>(p, k);
-          v[k] = TileBuf(ar.s8 + tb + kp, lim > kp ? lim - kp : 0u).ldb(o0);
-          if (!PLK_NTT_BYTE_LUT) v[k] = F::byte_val(v[k]);
-        }
-        return;
-      }
       const TileBuf bs(ar.s8 + tb, lim);
 #pragma unroll
-      for (int k = 0; k < G::E; k++) {
-        const uint32_t o = G::template toff_k<0, false>(p, o0, b0, k);
-        if ((PLK_NTT_DIAG & 8) && k > 0) { v[k] = (v[0] + k) & 0xFFu; continue; }
-        v[k] = bs.ldb(o);
-        if (!PLK_NTT_BYTE_LUT) v[k] = F::byte_val(v[k]);
-      }
+      for (int k = 0; k < G::E; k++) v[k] = bs.ldb(G::template toff_k<0, false>(p, o0, b0, k));
     } else {
       const TileBuf bd(ar.d + tb);
 #pragma unroll
@@ -996,7 +776,7 @@ __global__ __launch_bounds__(wt_nt(TB), TB == 13 && M == TB ? 4 : 8) void wt_fwd
   // block's first load can be one -- never a prefetch)
   // (2^13 tiles only: the 2^12-tile byte passes -- C3's poly_mul -- keep their registers, 36 VGPRs
   // instead of 40: poly_mul 2^19 x 2^19 +0.3 us with the branch compiled in)
-  if (PLK_NTT_DERIVE && TB == 13 && FROM_U8 && ai == 0 && arrs.derive) load_derived<G>(arrs, p, tb, o0, b0, v);
+  if (TB == 13 && FROM_U8 && ai == 0 && arrs.derive) load_derived<G>(arrs, p, tb, o0, b0, v);
   else load(ai, v);
   // column factor table words of the elements this thread stores (HIGH passes): the same for
   // every array of the block
@@ -1008,7 +788,7 @@ __global__ __launch_bounds__(wt_nt(TB), TB == 13 && M == TB ? 4 : 8) void wt_fwd
 #pragma unroll
     for (int k = 0; k < G::E; k++) {
       if constexpr (COLT) {
-        cl[k] = (PLK_NTT_DIAG & 16) ? 0x12345u + k : G::template ldk<G::NR - 1, false>(TileBuf(colt), p, of, bf, k);
+        cl[k] = G::template ldk<G::NR - 1, false>(TileBuf(colt), p, of, bf, k);
       } else {
         const uint32_t ex = G::col_exp(p, tile, bf + ((uint32_t)k << LF));
         cl[k] = tw.lo[ex & 4095u];
@@ -1016,20 +796,18 @@ __global__ __launch_bounds__(wt_nt(TB), TB == 13 && M == TB ? 4 : 8) void wt_fwd
       }
     }
   }
-  __shared__ uint32_t lut[FROM_U8 && PLK_NTT_BYTE_LUT ? 256 : 1];
-  if (FROM_U8 && PLK_NTT_BYTE_LUT && tid < 256) lut[tid] = F::byte_val(tid);
+  // a byte's value through a 256-entry table
+  __shared__ uint32_t lut[FROM_U8 ? 256 : 1];
+  if (FROM_U8 && tid < 256) lut[tid] = F::byte_val(tid);
   if constexpr (PW) load_pass_tw_pairs<M, G::NT>(Tsm, tw.small);
   else load_pass_tw<M, G::NT>(Tsm, tw.small);
-  // exchange layout: the lo = 0 pass of a standalone transform may take the pass-wide swizzle
-  constexpr int XSWZ = M == TB && PLK_NTT_LO_USWZ ? 4 : 1;
-  // (xc continues over the arrays: with alternating buffers the one an array's first exchange
-  // writes was last read before the previous array's last exchange barrier -- no barrier needed)
-  constexpr bool ALT = PLK_NTT_ALT_ARRAYS && G::DBUF && XSWZ < 3;
+  // exchange layout: the lo = 0 pass (of a standalone transform) takes the pass-wide swizzle
+  constexpr XLayout XL = M == TB ? X_SWZ_PASS : X_SWZ_EACH;
   for (int q = 0;; q++) {
-    // (q = 0: the tables are in LDS; q > 0 without ALT: every thread's reads of the previous
-    // array's last exchange are done before this one's first exchange writes)
-    if (q == 0 || !ALT) __syncthreads();
-    if constexpr (FROM_U8 && PLK_NTT_BYTE_LUT) {
+    // (q = 0: the tables are in LDS; q > 0: every thread's reads of the previous array's last
+    // exchange are done before this one's first exchange writes)
+    __syncthreads();
+    if constexpr (FROM_U8) {
 #pragma unroll
       for (int k = 0; k < G::E; k++) v[k] = lut[v[k]];
     }
@@ -1037,8 +815,8 @@ __global__ __launch_bounds__(wt_nt(TB), TB == 13 && M == TB ? 4 : 8) void wt_fwd
     // the next array's loads go out before this one's rounds, so their latency hides behind the
     // butterflies (the barriers wait for LDS only: the loads stay in flight across them)
     uint32_t nv[G::E];
-    if (PLK_NTT_PREFETCH && more) load(ai + 1, nv);
-    G::template pass<false, XSWZ, PW, true>(v, tid, bufs, ALT ? q * G::XCH : 0, Tsm);
+    if (more) load(ai + 1, nv);
+    G::template pass<false, XL, PW, true>(v, tid, bufs, Tsm);
     const TileBuf bd(arrs.a[ai].d + tb);
 #pragma unroll
     for (int k = 0; k < G::E; k++) {
@@ -1050,83 +828,21 @@ __global__ __launch_bounds__(wt_nt(TB), TB == 13 && M == TB ? 4 : 8) void wt_fwd
     }
     if (!more) break;
     ++ai;
-    if constexpr (PLK_NTT_PREFETCH) {
 #pragma unroll
-      for (int k = 0; k < G::E; k++) v[k] = nv[k];
-    } else {
-      load(ai, v);
-    }
+    for (int k = 0; k < G::E; k++) v[k] = nv[k];
   }
-}
-
-
-// Wrapped products (la + lb - 1 = N + ntop): the last inverse pass wrote c[j] + c[N + j] mod 17
-// at j < ntop.  c[N + j] (sum group: of the group's sum) has only the terms a[i] b[N + j - i]
-// with i > N + j - lb (ntop - j <= 16 of them): computed from the bytes after the pass, by this
-// small launch (round 4: inlined into the pass kernel, its loops held registers in the hot path).
-// Block = job (jobs without a wrapped top return at once), thread j < ntop = position j; a job
-// with a trimmed-length word takes the positions' maximum into it (the pass left them out).
-// Every term a[i] b[N + j - i] of c[N + j] (j < ntop <= 16) has i in the top 16 bytes of a and
-// N + j - i in the top 16 of b (la + lb - 1 - N <= 16, also for a group's shorter members): the
-// block stages those bytes in LDS with ONE load each, then thread j sums from LDS -- one memory
-// round trip for the whole fix (a loop of dependent byte loads per term took ~5 us per launch).
-__global__ __launch_bounds__(64) void wrap_fix_kernel(WJobs jobs, uint64_t N) {
-  const WJob& jb = jobs.j[blockIdx.x];
-  const uint32_t ntop = (uint32_t)jb.ntop;
-  if (!ntop) return;   // (uniform: a job without a wrapped top)
-  __shared__ uint32_t A[3][16], B[3][16];   // [member][q] = byte la - 16 + q (0 below index 0)
-  const uint32_t t = threadIdx.x;
-  if (t < 48) {
-    const int g = (int)(t >> 4), q = (int)(t & 15);
-    uint32_t va = 0, vb = 0;
-    if (g <= jb.ngroup) {
-      const uint8_t* a = g ? jb.ga8[g - 1] : jb.a8;
-      const uint8_t* b = g ? jb.gb8[g - 1] : jb.b8;
-      const uint64_t la = g ? jb.gla[g - 1] : jb.la, lb = g ? jb.glb[g - 1] : jb.lb;
-      if (la + (uint64_t)q >= 16) va = a[la - 16 + q] % 17u;
-      if (lb + (uint64_t)q >= 16) vb = b[lb - 16 + q] % 17u;
-    }
-    A[g][q] = va;
-    B[g][q] = vb;
-  }
-  const uint32_t j = t;
-  const uint32_t cur = j < ntop ? jb.out8[j] : 0u;   // (c[j] + c[N + j] mod 17, the pass's byte)
-  __syncthreads();
-  if (j >= ntop) return;
-  uint32_t s = 0;
-  for (int g = 0; g <= jb.ngroup; g++) {
-    const uint64_t la = g ? jb.gla[g - 1] : jb.la, lb = g ? jb.glb[g - 1] : jb.lb;
-    if (la + lb - 1 <= N + j) continue;   // (a shorter member: no term reaches c[N + j])
-    // i in [N + j + 1 - lb, la): q = i - la + 16, b index N + j - i = lb - 16 + (16 + N + j + lb... )
-    const int d = (int)(la + lb - 1 - N - j);   // terms: i = la - d .. la - 1 (d <= 16)
-#pragma unroll
-    for (int u = 0; u < 16; u++) {
-      // i = la - d + u: a at q = 16 - d + u, b index N + j - i = lb - 1 - u: q = 15 - u
-      if (u < d) s += A[g][16 - d + u] * B[g][15 - u];
-    }
-  }
-  s %= 17u;
-  const uint32_t lo = (cur + 17u - s) % 17u;
-  jb.out8[j] = (uint8_t)lo;
-  jb.out8[N + j] = (uint8_t)s;
-  uint32_t last = lo ? j + 1u : 0u;
-  if (s) last = (uint32_t)(N + j) + 1u;
-  if (jb.nz && last) atomicMax(jb.nz, last);
 }
 
 // Inverse (DIT) pass, u32 in place (the job's C); the final pass (TO_U8) scales by N^-1 (normal form,
 // which also leaves Montgomery form), reduces mod 17 and writes bytes for idx < out_len.
 // COLT (final passes only): the column table is the inverse one, whose factors carry that scale
-// (the pass is linear), so the bytes come from the pass's outputs directly (F::out17s).
+// (the pass is linear), so the bytes come from the pass's outputs directly (F::out17_idx).
 // Block (x, y) runs tile x of jobs y jpb .. y jpb + jpb - 1 (< nj) one after another, loading the
 // column factors and stage twiddles once for all of them.
 template <int TB, int R, int M, bool TO_U8, class F, bool COLT = false>
 __global__ __launch_bounds__(wt_nt(TB), 8) void wt_inv_kernel(WPass p, WJobs jobs, WTw tw, uint32_t ninv, int nj, int jpb) {
   using G = Eng<TB, R, M, F>;
   static_assert(G::NT == wt_nt(TB), "tile block size");
-  // prefetch where the registers allow it: the wide byte-output passes have none to spare (their
-  // spill reloads would wait for the prefetched loads anyway)
-  constexpr bool PF = PLK_NTT_PREFETCH_INV && !(TO_U8 && (M > 8 || M < 4));
   __shared__ uint32_t Tsm[1 << M];
   __shared__ uint32_t bufs[G::nbuf() * G::BUF];
   const uint32_t tid = threadIdx.x;
@@ -1147,9 +863,8 @@ __global__ __launch_bounds__(wt_nt(TB), 8) void wt_inv_kernel(WPass p, WJobs job
   };
   load(ji, v);   // (the first job's loads go out before the tables')
   uint32_t cl[G::HIGH ? G::E : 1], ch[G::HIGH && !COLT ? G::E : 1];
-  if constexpr (G::HIGH && COLT && PLK_NTT_COLI_DERIVE && G::colsq(0, true)) {
-    // The scaled column factors without the table (the 2^22 table is 16 MiB read per
-    // launch).  Round 0 is column-mapped: a thread's E words share their column L and differ only in
+  if constexpr (G::HIGH && COLT && G::colsq(0, true)) {
+    // The scaled column factors without the table (the 2^22 table is 16 MiB read per launch).  Round 0 is column-mapped: a thread's E words share their column L and differ only in
     // the row bits [L0, L0 + R), so their exponents are ex0 + sum over the set register bits b of d_b
     // (bitrev of disjoint bits adds).  cl[0] = scale(w^ex0) from the lo / hi roots, d_b's roots the
     // same way, then each cl[k] = cl[k - 2^b] * w^(d_b) for k's top bit b: R + 1 root lookups and
@@ -1179,15 +894,14 @@ __global__ __launch_bounds__(wt_nt(TB), 8) void wt_inv_kernel(WPass p, WJobs job
   }
   load_pass_tw<M, G::NT>(Tsm, tw.small);
   // (COLT byte outputs) x mod 17 for x < M17_LUT, read at F::out17_idx
-  __shared__ uint8_t m17[TO_U8 && COLT && PLK_NTT_M17 ? M17_LUT : 1];
-  if constexpr (TO_U8 && COLT && PLK_NTT_M17) {
+  __shared__ uint8_t m17[TO_U8 && COLT ? M17_LUT : 1];
+  if constexpr (TO_U8 && COLT) {
     for (uint32_t i = tid; i < M17_LUT; i += G::NT) m17[i] = (uint8_t)(i % 17u);
   }
   const uint32_t bf = G::template base_q<G::NR - 1>(tid, true);
   const uint32_t of = G::toff(p, bf);
   const uint32_t N = 1u << p.k;   // (k <= 27: every index fits 32 bits)
-  constexpr int XSWZ = M == TB && PLK_NTT_LO_USWZ ? 4 : 1;
-  constexpr bool ALT = PLK_NTT_ALT_ARRAYS && G::DBUF && XSWZ < 3;
+  constexpr XLayout XL = M == TB ? X_SWZ_PASS : X_SWZ_EACH;   // (wt_fwd_kernel)
   for (int q = 0;; q++) {
     const WJob& jb = jobs.j[ji];   // (sum-group members are not in the grid: no inverse of their own)
     uint8_t* out8 = jb.out8;
@@ -1214,13 +928,9 @@ __global__ __launch_bounds__(wt_nt(TB), 8) void wt_inv_kernel(WPass p, WJobs job
       }
     }
     const bool more = q + 1 < jpb && ji + 1 < nj;   // (uniform)
-    // the next job's loads before this one's rounds (wt_fwd_kernel)
-    uint32_t nv[G::E];
-    if (PF && more) load(ji + 1, nv);
-    // (q = 0: the stage twiddles are in LDS; q > 0 without ALT: the previous job's last exchange
-    // reads are done; with ALT the buffers alternate over the jobs, wt_fwd_kernel)
-    if (q == 0 || !ALT) __syncthreads();
-    G::template pass<true, XSWZ>(v, tid, bufs, ALT ? q * G::XCH : 0, Tsm);
+    // (q = 0: the stage twiddles are in LDS; q > 0: the previous job's last exchange reads are done)
+    __syncthreads();
+    G::template pass<true, XL>(v, tid, bufs, Tsm);
     uint32_t last = 0;      // 1 + the largest index this thread left a non-zero byte at
     const uint32_t lim = out_len < N ? (uint32_t)out_len : N;
     const uint32_t ntop = (uint32_t)jb.ntop;   // (read once: the byte stores below may alias the job table)
@@ -1239,13 +949,12 @@ __global__ __launch_bounds__(wt_nt(TB), 8) void wt_inv_kernel(WPass p, WJobs job
 #pragma unroll
       for (int k = 0; k < G::E; k++) {
         jj[k] = (N - ((uint32_t)tb + G::template toff_k<G::NR - 1, true>(p, of, bf, k))) & (N - 1);
-        rr[k] = !COLT ? F::out17(v[k], ninv)
-                : PLK_NTT_M17 ? (uint32_t)m17[F::out17_idx(v[k])] : mod17_small(F::out17_idx(v[k]));
+        rr[k] = !COLT ? F::out17(v[k], ninv) : (uint32_t)m17[F::out17_idx(v[k])];
       }
 #pragma unroll
       for (int k = 0; k < G::E; k++) bo.stb(jj[k], rr[k]);
       // the trimmed length only when the job has one (uniform: the prover's batched products do
-      // not; the wrapped positions j < ntop are fixed, and counted, by wrap_fix_kernel)
+      // not; the wrapped positions j < ntop are fixed, and counted, after the block's jobs below)
       if (jb.nz) {
 #pragma unroll
         for (int k = 0; k < G::E; k++) last = max(last, (jj[k] < lim && jj[k] >= ntop && rr[k]) ? jj[k] + 1u : 0u);
@@ -1267,16 +976,14 @@ __global__ __launch_bounds__(wt_nt(TB), 8) void wt_inv_kernel(WPass p, WJobs job
     }
     if (!more) break;
     ++ji;
-    if constexpr (PF) {
-#pragma unroll
-      for (int k = 0; k < G::E; k++) v[k] = nv[k];
-    } else {
-      load(ji, v);
-    }
+    load(ji, v);
   }
-#if PLK_NTT_WRAP_INLINE
-  // Wrapped tops (wrap_fix_kernel's work, done by the block whose tile holds the position, after
-  // its jobs: no launch of its own).  Position j < ntop is element (N - j) mod N.
+  // Wrapped products (la + lb - 1 = N + ntop, ntop <= 16): the pass wrote c[j] + c[N + j] mod 17 at
+  // j < ntop.  c[N + j] (sum group: of the group's sum) has only the terms a[i] b[N + j - i] with
+  // i > N + j - lb -- ntop - j <= 16 of them, from the top 16 bytes of each operand -- so it is
+  // computed from the bytes and both ends are corrected, by the block whose tile holds the
+  // position, after its jobs.  Position j < ntop is element (N - j) mod N.  A job with a
+  // trimmed-length word takes the positions' maximum into it (the pass left them out).
   if constexpr (TO_U8) {
     const int j0 = (int)blockIdx.y * jpb;
     bool any = false;
@@ -1324,7 +1031,6 @@ __global__ __launch_bounds__(wt_nt(TB), 8) void wt_inv_kernel(WPass p, WJobs job
       }
     }
   }
-#endif
 }
 
 // Center of poly_mul: last forward pass (lo = 0) of a and b, pointwise product (plus a merged
@@ -1336,24 +1042,19 @@ __global__ __launch_bounds__(wt_nt(TB), 8) void wt_inv_kernel(WPass p, WJobs job
 // halves the block's LDS so that two blocks fit a CU.
 // GRP: the launch has merged sum groups (the item loop's per-pair steps; without, one pair)
 template <int TB, int R, class F, bool GRP>
-__global__ __launch_bounds__(wt_ntc(TB), TB == 13 ? PLK_NTT_CW13 : 1) void wt_center_kernel(WPass p, WJobs jobs,
-                                                                                                     WTw twf, WSched sc) {
+__global__ __launch_bounds__(wt_ntc(TB), TB == 13 ? WT_CENTER13_WAVES : 1) void wt_center_kernel(WPass p, WJobs jobs,
+                                                                                                         WTw twf, WSched sc) {
   using G = Eng<TB, R, TB, F>;
   static_assert(G::NT == wt_ntc(TB), "tile block size");
   static_assert(G::lbq(G::NR - 1, false) == 0 && G::lbq(0, true) == 0, "center mapping");
-  constexpr int CSWZ = TB == 13 ? PLK_NTT_CENTER_SWZ : PLK_NTT_CENTER_SWZ12;
-  constexpr bool UNI = CSWZ >= 3;   // one layout, barriers only where sets change (Eng::same_sets)
-  // (UNI, 2^12 tiles, PLK_NTT_CENTER12_2BUF) b's pass in a buffer of its own: a's last reads and b's
-  // first writes cannot meet, so no barrier between the two forward passes (the inverse pass, back in
-  // a's buffer, starts after b's first barrier, when every wave has left a's pass)
-  constexpr bool B2 = UNI && TB == 12 && PLK_NTT_CENTER12_2BUF;
-  static_assert(!B2 || !G::wave_local(0, false), "b's first exchange must carry the barrier that ends a's pass");
-  // (F29, PLK_NTT_CENTER_PW) the twiddle table's low stages as {w, p - w} pairs: the forward DIF
-  // skips its p - w subtraction there; 2^11 pairs for 2^13 tiles keep two blocks per CU in LDS
-  constexpr int CPWB = F::ADIC != f29::TWO_ADICITY ? 0
-                       : TB == 13 ? ((PLK_NTT_CENTER_PW & 2) ? 11 : 0) : ((PLK_NTT_CENTER_PW & 1) ? TB : 0);
-  __shared__ __attribute__((aligned(16))) uint32_t Tlds[(1 << TB) + (CPWB ? (1 << CPWB) : 0)];
-  __shared__ uint32_t bufs[(G::DBUF && (!UNI || B2) ? 2 : 1) * G::BUF];
+  // one exchange layout per tile size, one buffer, barriers only where a wave's element set changes
+  // (Eng::same_sets)
+  constexpr XLayout CXL = wt_center_layout(TB);
+  // 2^12 tiles in F29: the twiddle table as {w, p - w} pairs, so the forward DIF skips its p - w
+  // subtraction (2^13 tiles: single words, which keep two blocks per CU in LDS)
+  constexpr bool CPW = F::ADIC == f29::TWO_ADICITY && TB == 12;
+  __shared__ __attribute__((aligned(16))) uint32_t Tlds[(CPW ? 2 : 1) << TB];
+  __shared__ uint32_t bufs[G::BUF];
   const uint32_t* Tf = Tlds;
   const uint32_t tid = threadIdx.x;
   const uint32_t b0 = G::template base_q<0>(tid, false);
@@ -1367,16 +1068,8 @@ __global__ __launch_bounds__(wt_ntc(TB), TB == 13 ? PLK_NTT_CW13 : 1) void wt_ce
   if (blockIdx.x == 0 && tid < (uint32_t)sc.nj && jobs.j[tid].nz) *jobs.j[tid].nz = 0u;
   // the twiddle table first (a "first item" flag inside the loop had the compiler hoist the
   // table's addresses out of the loop and spill them)
-  if constexpr (CPWB) load_center_tw<TB, CPWB, G::NT>(Tlds, twf.small);
+  if constexpr (CPW) load_pass_tw_pairs<TB, G::NT>(Tlds, twf.small);
   else load_pass_tw<TB, G::NT>(Tlds, twf.small);
-  // the item after `it` in this block's stride that has a job (items of padding slots skipped)
-  auto next_item = [&](uint32_t it) {
-    for (it += gridDim.x; it < items && sc.job[it / tiles] < 0; it += gridDim.x) {
-    }
-    return it;
-  };
-  uint32_t pa[G::E];   // (PLK_NTT_CENTER_PF) the next item's A words, loaded during this item's inverse rounds
-  bool have = false;   // (uniform) pa holds this item's A
   for (uint32_t it = blockIdx.x; it < items; it += gridDim.x) {
     const uint32_t slot = it / tiles, tile = it - slot * tiles;
     const int job = sc.job[slot];
@@ -1386,36 +1079,28 @@ __global__ __launch_bounds__(wt_ntc(TB), TB == 13 ? PLK_NTT_CW13 : 1) void wt_ce
     const uint64_t tb = (uint64_t)tile << TB;
     const TileBuf b_c(J.C + tb);
     uint32_t va[G::E], vb[G::E];
-    int xc = 0;
     // the job's pair, then a merged sum group's members' pairs: each pointwise product but the
     // last is parked in the job's C tile (its own positions; C is no operand of the group) and
     // added to the next one, so two register arrays suffice
     for (int q = 0;; q++) {
       const WJob& P = jobs.j[q ? J.cm[q - 1] : job];
       const TileBuf b_a(P.A + tb), b_b(P.B + tb);
-      // (a block's first item loads its A here; later ones found it prefetched)
-      const bool pre = PLK_NTT_CENTER_PF && q == 0 && have;
 #pragma unroll
       for (int k = 0; k < G::E; k++) {
-        va[k] = pre ? pa[k] : b_a.ld(b0, (uint32_t)k << L0);   // (the per-register part in the SGPR offset)
+        va[k] = b_a.ld(b0, (uint32_t)k << L0);   // (the per-register part in the SGPR offset)
         vb[k] = b_b.ld(b0, (uint32_t)k << L0);
       }
-      // (the previous item's or pair's last exchange reads; with UNI the previous pair's too.
-      // Skipping it where Eng::same_sets allows -- the inverse's last round and the forward's first
-      // give the waves the same sets -- measured no faster: kept)
-      if (q == 0 || UNI) __syncthreads();
+      // (the previous item's or pair's last exchange reads.  Skipping it where Eng::same_sets
+      // allows -- the inverse's last round and the forward's first give the waves the same sets --
+      // measured no faster: kept)
+      __syncthreads();
       // (afix / bfix: the operand's transform is finished -- plk_wave_pretransform / wt_fixfwd_kernel
-      // stored this pass's output registers where their inputs were read -- so its pass is
-      // skipped; xc counts the exchanges so that double buffers keep alternating)
-      if (!P.afix) {
-        G::template pass<false, CSWZ, false, false, CPWB>(va, tid, bufs, xc, Tf);
-        xc += G::XCH;
-      }
+      // stored this pass's output registers where their inputs were read -- so its pass is skipped)
+      if (!P.afix) G::template pass<false, CXL, CPW>(va, tid, bufs, Tf);
       if (!P.bfix) {
-        // (UNI: a's last reads against b's first writes)
-        if (UNI && !B2 && !P.afix && !G::same_sets(G::NR - 1, false, 0, false)) __syncthreads();
-        G::template pass<false, CSWZ, false, false, CPWB>(vb, tid, B2 ? bufs + G::BUF : bufs, xc, Tf);
-        xc += G::XCH;
+        // (a's last reads against b's first writes)
+        if (!P.afix && !G::same_sets(G::NR - 1, false, 0, false)) __syncthreads();
+        G::template pass<false, CXL, CPW>(vb, tid, bufs, Tf);
       }
 #pragma unroll
       for (int k = 0; k < G::E; k++) va[k] = F::pmul(va[k], vb[k]);
@@ -1428,21 +1113,9 @@ __global__ __launch_bounds__(wt_ntc(TB), TB == 13 ? PLK_NTT_CW13 : 1) void wt_ce
       for (int k = 0; k < G::E; k++) b_c.st(b0, (uint32_t)k << L0, va[k]);
       __builtin_amdgcn_s_waitcnt(0);   // (the parked words are this thread's own: stored before reloaded)
     }
-    if (PLK_NTT_CENTER_PF) {
-      // the next item's A goes out before this one's inverse rounds (no job writes an array
-      // another job reads, and the same job's next item is another tile)
-      const uint32_t nit = next_item(it);
-      have = nit < items;
-      if (have) {
-        const uint32_t ns = nit / tiles;
-        const TileBuf b_n(jobs.j[sc.job[ns]].A + ((uint64_t)(nit - ns * tiles) << TB));
-#pragma unroll
-        for (int k = 0; k < G::E; k++) pa[k] = b_n.ld(b0, (uint32_t)k << L0);
-      }
-    }
-    // (UNI: the forward passes' last reads against the inverse pass's first writes)
-    if (UNI && !G::same_sets(G::NR - 1, false, 0, true)) __syncthreads();
-    G::template pass<true, CSWZ, false, false, CPWB>(va, tid, bufs, xc, Tf);
+    // (the forward passes' last reads against the inverse pass's first writes)
+    if (!G::same_sets(G::NR - 1, false, 0, true)) __syncthreads();
+    G::template pass<true, CXL, CPW>(va, tid, bufs, Tf);
 #pragma unroll
     for (int k = 0; k < G::E; k++) b_c.st(bf, (uint32_t)k << LF, va[k]);
   }
@@ -1453,14 +1126,12 @@ __global__ __launch_bounds__(wt_ntc(TB), TB == 13 ? PLK_NTT_CW13 : 1) void wt_ce
 // them unchanged: WJob::bfix / afix).  In place: every position is read and written by one
 // thread.  blockIdx.y = which array.
 template <int TB, int R, class F>
-__global__ __launch_bounds__(wt_ntc(TB), TB == 13 ? PLK_NTT_CW13 : 1) void wt_fixfwd_kernel(WPass p, WArrs arrs,
-                                                                                                    WTw twf) {
+__global__ __launch_bounds__(wt_ntc(TB), TB == 13 ? WT_CENTER13_WAVES : 1) void wt_fixfwd_kernel(WPass p, WArrs arrs,
+                                                                                                         WTw twf) {
   using G = Eng<TB, R, TB, F>;
-  constexpr int CSWZ0 = TB == 13 ? PLK_NTT_CENTER_SWZ : PLK_NTT_CENTER_SWZ12;
-  constexpr int CSWZ = CSWZ0 >= 3 ? CSWZ0 : 0;
   uint32_t* d = arrs.a[blockIdx.y].d;
   __shared__ uint32_t Tlds[1 << TB];
-  __shared__ uint32_t bufs[(G::DBUF && CSWZ < 3 ? 2 : 1) * G::BUF];
+  __shared__ uint32_t bufs[G::BUF];
   const uint32_t tid = threadIdx.x, tile = blockIdx.x;
   const uint32_t b0 = G::template base_q<0>(tid, false);
   constexpr int L0 = G::lbq(0, false);
@@ -1470,7 +1141,7 @@ __global__ __launch_bounds__(wt_ntc(TB), TB == 13 ? PLK_NTT_CW13 : 1) void wt_fi
   for (int k = 0; k < G::E; k++) v[k] = bt.ld(b0, (uint32_t)k << L0);
   load_pass_tw<TB, G::NT>(Tlds, twf.small);
   __syncthreads();
-  G::template pass<false, CSWZ>(v, tid, bufs, G::XCH, Tlds);
+  G::template pass<false, wt_center_layout(TB)>(v, tid, bufs, Tlds);
 #pragma unroll
   for (int k = 0; k < G::E; k++) bt.st(b0, (uint32_t)k << L0, v[k]);
 }
@@ -1505,7 +1176,7 @@ uint32_t center_blocks() {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     // the resident blocks: the launch bound's waves per SIMD x 4 SIMDs over the block's waves
-    const uint32_t per_cu = std::max<uint32_t>(1u, (uint32_t)PLK_NTT_CW13 * 4u * 64u / (uint32_t)wt_ntc(13));
+    const uint32_t per_cu = std::max<uint32_t>(1u, (uint32_t)WT_CENTER13_WAVES * 4u * 64u / (uint32_t)wt_ntc(13));
     nb = per_cu * (uint32_t)(cus > 0 ? cus : 256);
     resident.store(nb, std::memory_order_relaxed);
   }
@@ -1527,9 +1198,6 @@ int wave_plan(int k, int TB, int* Ms) {
 bool two_pass(int k) { return k - tile_bits(k) <= (tile_bits(k) == 12 ? WT_MAX_HI12 : WT_MAX_HI13); }
 
 // column tables [field][k] (field 0 BabyBear, 1 F29) for the 2-pass plans, k = 13 .. 23
-#ifndef PLK_NTT_COLT_MIN_K
-#define PLK_NTT_COLT_MIN_K 13   // smallest transform using a column table (tuning: larger = lo * hi products)
-#endif
 constexpr int COLT_MIN_K = 13, COLT_MAX_K = 23;
 // per device (plk_cur_device: the calling thread's current device)
 uint32_t* g_col[PLK_MAX_DEVICES][2][COLT_MAX_K + 1] = {};
@@ -1545,7 +1213,7 @@ WTw fwd_wtw(int k) {
   WTw w = to_wtw(f29 ? plk_ntt_tables29() : plk_ntt_tables(), false);
   // (a table holds the factors of the plan's ONE high pass: a three-pass plan's top pass -- 2^12
   // tiles above 2^20 when PLK_OPT_NTT_T13_MIN_K moves the 2^13 threshold up -- multiplies lo * hi)
-  w.col = (k >= PLK_NTT_COLT_MIN_K && k >= COLT_MIN_K && k <= COLT_MAX_K && two_pass(k))
+  w.col = (k >= COLT_MIN_K && k <= COLT_MAX_K && two_pass(k))
               ? g_col[plk_cur_device()][f29 ? 1 : 0][k]
               : nullptr;
   return w;
@@ -1782,7 +1450,7 @@ int wave_poly_mul_t(const WJobs& jobs, int nj, int k, uint32_t ninv, hipStream_t
     if (!jobs.j[j].der) continue;
     int q = 0;
     while (q < na && arrs.a[q].d != jobs.j[j].A) q++;
-    if (!PLK_NTT_DERIVE || TB != 13 || arrs.derive || np < 2 || q == na || jobs.j[j].der->la < 1) {
+    if (TB != 13 || arrs.derive || np < 2 || q == na || jobs.j[j].der->la < 1) {
       plk_set_error("wave poly_mul: a derived operand needs 2^13 tiles, one per batch and two or more passes "
                     "(2^%d: %d-bit tiles, %d passes)", k, TB, np);
       return PLK_ERR_ARG;
@@ -1824,23 +1492,6 @@ int wave_poly_mul_t(const WJobs& jobs, int nj, int k, uint32_t ninv, hipStream_t
         if (!jobs.j[j].bfix && cj.j[j].B == arrs.a[q].d) cj.j[j].bfix = 1;
       }
     }
-    // (PLK_NTT_FIX_FILL) the launch runs ceil(ns tiles / resident) rounds of resident blocks: fill its
-    // last round with operands used once, whose lo = 0 pass then leaves the centre items
-    if (PLK_NTT_FIX_FILL && ns) {
-      const uint32_t per = std::max<uint32_t>(1u, center_blocks() / std::max<uint32_t>(tiles, 1u));
-      int extra = (int)(((uint32_t)ns + per - 1) / per * per) - ns;
-      for (int q = arrs.derive ? 1 : 0; q < na && extra > 0 && ns < WT_MAX_ARRS; q++) {
-        bool fixed = false;
-        for (int t = 0; t < ns; t++) fixed |= sh.a[t].d == arrs.a[q].d;
-        if (fixed) continue;
-        sh.a[ns++] = arrs.a[q];
-        extra--;
-        for (int j = 0; j < nj; j++) {
-          if (cj.j[j].A == arrs.a[q].d) cj.j[j].afix = 1;
-          if (!jobs.j[j].bfix && cj.j[j].B == arrs.a[q].d) cj.j[j].bfix = 1;
-        }
-      }
-    }
     if (ns) {
       log_launch<F>(3, TB, TB, k, ns, 1, ns);
       hipLaunchKernelGGL((wt_fixfwd_kernel<TB, wt_rc(TB), F>), dim3(tiles, ns), dim3(wt_ntc(TB)), 0, st, WPass{k, 0}, sh,
@@ -1880,12 +1531,6 @@ int wave_poly_mul_t(const WJobs& jobs, int nj, int k, uint32_t ninv, hipStream_t
     rc = i == 0 ? inv_m<TB, true, F>(Ms[i], p, jj, ni, twi, ninv, st)
                 : inv_m<TB, false, F>(Ms[i], p, jj, ni, twf, 0u, st);
     if (rc) return rc;
-  }
-  bool wrapped = false;
-  for (int j = 0; j < ni; j++) wrapped |= ic.j[j].ntop > 0;
-  if (wrapped && !PLK_NTT_WRAP_INLINE) {   // (after the last inverse pass's byte stores, on the same stream)
-    hipLaunchKernelGGL(wrap_fix_kernel, dim3(ni), dim3(64), 0, st, ic, 1ull << k);
-    PLK_HIP(hipGetLastError());
   }
   return PLK_OK;
 }

@@ -105,6 +105,46 @@ def test_forward_vs_numpy_reference(hip, k):
     assert np.array_equal(back, (x.astype(np.uint64) * np.uint64(1 << k)) % np.uint64(P))
 
 
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 8, 12])
+def test_small_vs_numpy_reference(hip, k):
+    """The one-workgroup transform (2^k <= 2^12 points; k = 1 loads word by word, the others four
+    at a time; rounds of 4, 3, 2 and 1 stages) bit-exactly against the independent transform, and
+    the unscaled inverse against n x."""
+    import torch
+    rng = np.random.default_rng(300 + k)
+    x = rng.integers(0, P, 1 << k, dtype=np.int64)
+    d = torch.from_numpy(x.astype(np.int32)).cuda()
+    st = torch.cuda.current_stream()
+    hip.ntt_dev(d, k, False, st)
+    torch.cuda.synchronize()
+    got = d.cpu().numpy().view(np.uint32).astype(np.uint64)
+    assert np.array_equal(got, ntt_dif_reference(x, k)), k
+    hip.ntt_dev(d, k, True, st)
+    torch.cuda.synchronize()
+    back = d.cpu().numpy().view(np.uint32).astype(np.uint64)
+    assert np.array_equal(back, (x.astype(np.uint64) * np.uint64(1 << k)) % np.uint64(P)), k
+
+
+def test_small_batch_vs_numpy_reference(hip):
+    """One batched call of 3 arrays of 2^5 points: every array against the independent transform,
+    forward and (unscaled) inverse."""
+    import torch
+    k, batch = 5, 3
+    rng = np.random.default_rng(305)
+    x = rng.integers(0, P, (batch, 1 << k), dtype=np.int64)
+    d = torch.from_numpy(x.astype(np.int32)).cuda()
+    st = torch.cuda.current_stream()
+    hip.ntt_batch_dev(d, k, batch, False, st)
+    torch.cuda.synchronize()
+    got = d.cpu().numpy().view(np.uint32).astype(np.uint64)
+    for b in range(batch):
+        assert np.array_equal(got[b], ntt_dif_reference(x[b], k)), b
+    hip.ntt_batch_dev(d, k, batch, True, st)
+    torch.cuda.synchronize()
+    back = d.cpu().numpy().view(np.uint32).astype(np.uint64)
+    assert np.array_equal(back, (x.astype(np.uint64) * np.uint64(1 << k)) % np.uint64(P))
+
+
 @pytest.mark.parametrize("k,batch", [(10, 3), (14, 9), (20, 8), (22, 3)])
 def test_batch_matches_single(hip, k, batch):
     """plk_ntt_batch_dev (arrays sharing each pass's launch, <= 8 per launch) is bit-identical
