@@ -23,7 +23,6 @@
 
 #include <algorithm>
 #include <initializer_list>
-#include <tuple>
 #include <utility>
 #include <string>
 #include <vector>
@@ -118,58 +117,24 @@ __global__ __launch_bounds__(256) void lincomb_kernel(LcArgs a, const uint8_t* _
   }
 }
 
-// p readable in whole 16-byte chunks up to len (16-byte aligned): one unconditional uint4
-// load at a clamped address, bytes past len masked
-__device__ __forceinline__ void load16_masked(const uint8_t* p, uint64_t len, uint64_t i, uint32_t (&w)[4]) {
+// p readable in whole 4 NW-byte chunks up to len (aligned to them): one unconditional load at a
+// clamped address, bytes past len masked
+template <int NW>
+__device__ __forceinline__ void loadw_masked(const uint8_t* p, uint64_t len, uint64_t i, uint32_t (&w)[NW]) {
   const bool in = i < len;
-  const uint4 q = *reinterpret_cast<const uint4*>(p + (in ? i : 0));
-  const uint32_t v[4] = {q.x, q.y, q.z, q.w};
+  uint32_t v[NW];
+  if constexpr (NW == 4) {
+    const uint4 q = *reinterpret_cast<const uint4*>(p + (in ? i : 0));
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+    static_assert(NW == 2, "8 or 16 bytes");
+    const uint2 q = *reinterpret_cast<const uint2*>(p + (in ? i : 0));
+    v[0] = q.x; v[1] = q.y;
+  }
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
+  for (int k = 0; k < NW; k++) {
     const int64_t cnt = in ? (int64_t)len - (int64_t)(i + 4 * k) : 0;   // valid bytes in word k
     w[k] = cnt >= 4 ? v[k] : (cnt <= 0 ? 0u : v[k] & ((1u << (8 * cnt)) - 1u));
-  }
-}
-// 16 coefficients per thread and iteration (uint4 loads / stores); every pointer 16-byte
-// aligned (checked on the host, else lincomb_kernel): load16's vec is true throughout this file.
-__global__ __launch_bounds__(256) void lincomb16_kernel(LcArgs a, const uint8_t* __restrict__ S) {
-  uint32_t cf[LC_MAX];
-#pragma unroll
-  for (int t = 0; t < LC_MAX; t++) cf[t] = t < a.nt ? S[a.slot[t]] : 0u;
-  const uint32_t sc = S[a.scale];
-  const uint32_t c0 = a.c0 >= 0 ? S[a.c0] : 0u, c1 = a.c1 >= 0 ? S[a.c1] : 0u;
-  const uint32_t x = a.twist >= 0 ? S[a.twist] : 1u;
-  uint32_t tw[16];   // x^k; x^i = 1 for i = 0 mod 16 when x != 0
-  pow16(x, tw);
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * 16;
-  for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16; i < a.out_len; i += stride) {
-    uint32_t acc[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) acc[k] = 0;
-    if (i == 0) { acc[0] = c0; acc[1] = c1; }
-#pragma unroll
-    for (int t = 0; t < LC_MAX; t++) {
-      if (t < a.nt && i < a.len[t]) {
-        uint32_t w[4];
-        load16(a.p[t], a.len[t], i, true, w);
-#pragma unroll
-        for (int k = 0; k < 16; k++) acc[k] += cf[t] * ((w[k >> 2] >> (8 * (k & 3))) & 0xFFu);
-      }
-    }
-    uint32_t o[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      uint32_t v = mod17(mod17(acc[k]) * sc);   // (acc <= 16 terms x 16 x 255 + 32 < 69632)
-      if (a.twist >= 0) v = mod17(v * (x == 0 ? (i + k == 0 ? 1u : 0u) : tw[k]));
-      o[k >> 2] |= v << (8 * (k & 3));
-    }
-    if (i + 16 <= a.out_len) {
-      *reinterpret_cast<uint4*>(a.out + i) = make_uint4(o[0], o[1], o[2], o[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 16; k++)
-        if (i + k < a.out_len) a.out[i + k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
-    }
   }
 }
 
@@ -316,7 +281,9 @@ __global__ __launch_bounds__(256) void t2a_kernel(const uint8_t* __restrict__ ab
   }
 }
 
-// several independent lincombs in one launch (blockIdx.y = which), all 16-byte aligned
+// several independent lincombs in one launch (blockIdx.y = which): 16 coefficients per thread and
+// iteration (uint4 loads / stores); every pointer 16-byte aligned (checked on the host, else
+// lincomb_kernel): load16's vec is true throughout this file.
 constexpr int LCB_MAX = 8;
 struct LcBatch {
   LcArgs a[LCB_MAX];
@@ -329,7 +296,7 @@ __global__ __launch_bounds__(256) void lincomb16_batch_kernel(LcBatch b, const u
   const uint32_t sc = S[a.scale];
   const uint32_t c0 = a.c0 >= 0 ? S[a.c0] : 0u, c1 = a.c1 >= 0 ? S[a.c1] : 0u;
   const uint32_t x = a.twist >= 0 ? S[a.twist] : 1u;
-  uint32_t tw[16];
+  uint32_t tw[16];   // x^k; x^i = 1 for i = 0 mod 16 when x != 0
   pow16(x, tw);
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * 16;
   for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16; i < a.out_len; i += stride) {
@@ -379,25 +346,10 @@ __global__ __launch_bounds__(256) void copy3_kernel(Copy3 c) {
 // Horner of src/poly.h:265-272 == sum c_i x^i mod 17; x^i = x^(i mod 16) for x != 0.
 constexpr int EV_MAX = 16;   // evaluations per launch (arrival words)
 constexpr int EV_ROWS = 24;  // grid rows: a long evaluation runs as several rows (EvArgs::grp)
-#ifndef PLK_SLICE_WORDS
-#define PLK_SLICE_WORDS 1   // numdiv_kernel: t_lo / t_mid / t_hi stored a word (or two halves) at a time
-#endif
-#ifndef PLK_EV_SPLIT
-#define PLK_EV_SPLIT 1   // long evaluations as several grid rows (make_evargs)
-#endif
-#ifndef PLK_CP_BX
-#define PLK_CP_BX 227   // commit_pack_kernel: blocks per MSM row at most (2048 / 9)
-#endif
-#ifndef PLK_MSM_ROW_LENS
-#define PLK_MSM_ROW_LENS 1   // commitment MSMs over each row's own length (0: the arena stride's cmax)
-#endif
-#ifndef PLK_EV_BLOCKS
-#define PLK_EV_BLOCKS 64
-#endif
-constexpr int EV_BLOCKS = PLK_EV_BLOCKS;   // x 256 threads x 4 uint4 loads in flight each
+constexpr int EV_BLOCKS = 64;   // x 256 threads x 4 uint4 loads in flight each
 constexpr int TICK_STRIDE = 32;   // one 128-byte line per arrival word
 constexpr int AGG_CHUNK = 4096;   // round 5's scan chunk (SCAN_B) as aggregated by the evaluation rows
-enum EvPost : int { EV_POST_NONE = 0, EV_POST_ACC = 1, EV_POST_R4 = 4 };
+enum EvPost : int { EV_POST_ACC = 1, EV_POST_R4 = 4 };
 struct EvArgs {
   const uint8_t* p[EV_ROWS];
   uint64_t len[EV_ROWS];
@@ -425,11 +377,11 @@ struct EvArgs {
 
 __device__ void scalars_r45(uint8_t* S, uint32_t tz);
 
-// Block bx of BX of evaluation e (eval_kernel's rows, or extra blocks of another launch): its
-// partial with a ticket to the row's arrival word; the row's last block writes S[out] and, with
-// `top`, takes a ticket on the top word -- whose last taker runs the round's scalar program.
+// Block bx of BX of evaluation e (eval_kernel's rows): its partial with a ticket to the row's
+// arrival word; the row's last block writes S[out] and takes a ticket on the top word -- whose
+// last taker runs the round's scalar program.
 __device__ __forceinline__ void eval_row_block(const EvArgs& a, int e, uint32_t bx, uint32_t BX, uint8_t* S,
-                                               uint32_t* tick, uint32_t* stat, bool top) {
+                                               uint32_t* tick, uint32_t* stat) {
   const uint32_t x = S[a.xslot[e]];
   uint32_t pw[16];
   pow16(x, pw);
@@ -449,7 +401,7 @@ __device__ __forceinline__ void eval_row_block(const EvArgs& a, int e, uint32_t 
     for (uint64_t c = (uint64_t)bx * (blockDim.x >> 6) + wv; c < nch; c += (uint64_t)BX * (blockDim.x >> 6)) {
       uint32_t w[4][4];
 #pragma unroll
-      for (int u = 0; u < 4; u++) load16_masked(p, n, c * AGG_CHUNK + u * 1024 + lane * 16, w[u]);
+      for (int u = 0; u < 4; u++) loadw_masked<4>(p, n, c * AGG_CHUNK + u * 1024 + lane * 16, w[u]);
       uint32_t s = 0;
 #pragma unroll
       for (int u = 0; u < 4; u++)
@@ -469,7 +421,7 @@ __device__ __forceinline__ void eval_row_block(const EvArgs& a, int e, uint32_t 
     for (uint64_t i0 = gid * 16; i0 < n; i0 += 4 * stride) {
       uint32_t w[4][4];
 #pragma unroll
-      for (int u = 0; u < 4; u++) load16_masked(p, n, i0 + u * stride, w[u]);
+      for (int u = 0; u < 4; u++) loadw_masked<4>(p, n, i0 + u * stride, w[u]);
 #pragma unroll
       for (int u = 0; u < 4; u++) {
         uint32_t s = 0;
@@ -512,7 +464,6 @@ __device__ __forceinline__ void eval_row_block(const EvArgs& a, int e, uint32_t 
   // the row's last block publishes the value: only these <= EV_MAX blocks fence
   S[a.out[e]] = (uint8_t)(((uint32_t)old + mine) % HFP);
   __threadfence();
-  if (!top) return;
   uint32_t* topw = tick + EV_MAX * TICK_STRIDE;
   if (atomicAdd(topw, 1u) != (uint32_t)a.ne - 1) return;
   __threadfence();
@@ -528,7 +479,7 @@ __device__ __forceinline__ void eval_row_block(const EvArgs& a, int e, uint32_t 
 // three-launch chain in one.
 __global__ __launch_bounds__(256) void eval_kernel(EvArgs a, uint8_t* __restrict__ S, uint32_t* __restrict__ tick,
                                                    uint32_t* __restrict__ stat) {
-  eval_row_block(a, (int)blockIdx.y, blockIdx.x, gridDim.x, S, tick, stat, true);
+  eval_row_block(a, (int)blockIdx.y, blockIdx.x, gridDim.x, S, tick, stat);
 }
 
 // (optional) commitments that do not wait for round 5, run as extra grid rows of round 5's
@@ -759,7 +710,7 @@ __global__ __launch_bounds__(256) void numdiv_kernel(LcArgs a, const uint8_t* __
       const int s0 = j0 < sl.part ? 0 : (j0 < 2 * sl.part ? 1 : 2);
       const uint64_t o0 = j0 - (uint64_t)s0 * sl.part;
       uint8_t* const d0 = sl.dst[s0] + o0;
-      if (PLK_SLICE_WORDS && skip[0] == 0 && skip[3] == 0 && o0 + 4 <= sl.len[s0] &&
+      if (skip[0] == 0 && skip[3] == 0 && o0 + 4 <= sl.len[s0] &&
           (s0 == 2 || o0 + 4 <= sl.part) && ((uintptr_t)d0 & 1) == 0) {
         if (((uintptr_t)d0 & 3) == 0) {
           *reinterpret_cast<uint32_t*>(d0) = o;
@@ -834,26 +785,6 @@ struct LinDivs {
 // bytes 0 / 2 and 1 / 3 as two 16-bit lanes (w & 0x00FF00FF, (w >> 8) & 0x00FF00FF) times cf[t] by
 // one 24-bit multiply each -- 16 x 16 x 255 + 32 < 2^16, so no lane carries into the next -- half
 // the multiplies and extracts of a per-byte loop.
-// p readable in whole 4 NW-byte chunks up to len (aligned to them): one unconditional load at a
-// clamped address, bytes past len masked (load16_masked for NW = 4)
-template <int NW>
-__device__ __forceinline__ void loadw_masked(const uint8_t* p, uint64_t len, uint64_t i, uint32_t (&w)[NW]) {
-  const bool in = i < len;
-  uint32_t v[NW];
-  if constexpr (NW == 4) {
-    const uint4 q = *reinterpret_cast<const uint4*>(p + (in ? i : 0));
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-    static_assert(NW == 2, "8 or 16 bytes");
-    const uint2 q = *reinterpret_cast<const uint2*>(p + (in ? i : 0));
-    v[0] = q.x; v[1] = q.y;
-  }
-#pragma unroll
-  for (int k = 0; k < NW; k++) {
-    const int64_t cnt = in ? (int64_t)len - (int64_t)(i + 4 * k) : 0;   // valid bytes in word k
-    w[k] = cnt >= 4 ? v[k] : (cnt <= 0 ? 0u : v[k] & ((1u << (8 * cnt)) - 1u));
-  }
-}
 template <int NW>
 __device__ __forceinline__ void lc_swar(const LcArgs& a, const uint32_t (&cf)[LC_MAX], uint32_t c0, uint32_t c1,
                                         uint64_t i, uint32_t (&acc)[4 * NW]) {
@@ -1153,7 +1084,8 @@ __global__ __launch_bounds__(256) void divide_general_kernel(const uint8_t* __re
 }
 
 // ------------------------------------------------------------------ trimmed lengths
-// one block per buffer: index + 1 of the last non-zero byte, at least 1 (src/poly.h:20-24)
+// The buffers trim_pack_kernel / commit_pack_kernel scan after the commitments: status word dst
+// gets index + 1 of the buffer's last non-zero byte, at least 1 (src/poly.h:20-24)
 // dst | TRIM_ANY: write 1 to the word if any byte is non-zero (a flag), leave it otherwise
 constexpr int TRIM_ANY = 1 << 16;
 struct TrimArgs {
@@ -1236,16 +1168,13 @@ __global__ void scalars_init_kernel(SlotFile f, uint8_t* __restrict__ S, uint32_
 // the MSM (which runs over the committed length and does not need them): wave w < ntrim finds
 // buffer w's last non-zero byte from the top, 1 KB per step (16 bytes per lane, the highest
 // non-zero lane by ballot); the remaining waves OR the remainder-vote bytes (TRIM_ANY).
-#ifndef PLK_DIAG_PACK_ONLY
-#define PLK_DIAG_PACK_ONLY 0   // timing builds only: 1 skips the trimmed-length scans (wrong status words)
-#endif
 constexpr int PACK_T = 1024;
 static_assert(NSTAT <= 64 && 34 <= 64, "trim_pack_kernel: wave 0 writes the status words, the last wave the proof");
 __global__ __launch_bounds__(PACK_T) void trim_pack_kernel(TrimArgs a, int nt, const PlkMsmResult* __restrict__ res,
                                                            const uint8_t* __restrict__ S, uint32_t* __restrict__ stat,
                                                            uint8_t* __restrict__ host, uint32_t seq) {
   const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
-  const int ntrim = PLK_DIAG_PACK_ONLY ? 0 : nt > 0 && (a.dst[nt - 1] & TRIM_ANY) ? nt - 1 : nt;   // the vote buffer comes last
+  const int ntrim = nt > 0 && (a.dst[nt - 1] & TRIM_ANY) ? nt - 1 : nt;   // the vote buffer comes last
   // the proof bytes do not depend on the trimmed lengths: the last waves load and send them to
   // the host first, so their round trips overlap the scans below
   if (wv == PACK_T / 64 - 1) {
@@ -1310,6 +1239,7 @@ __global__ __launch_bounds__(PACK_T) void trim_pack_kernel(TrimArgs a, int nt, c
 // the status words into the mapped host buffer and writes the completion word, as
 // trim_pack_kernel does -- its launch and its scan latency leave the proof's tail.
 constexpr int CP_T = 256;
+constexpr int CP_BX = 227;   // blocks per MSM row at most (2048 / 9)
 __global__ __launch_bounds__(CP_T) void commit_pack_kernel(const uint8_t* __restrict__ logs, const uint8_t* arena,
                                                            uint64_t cstride, MsmRowLens rl, PlkMsmResult* res,
                                                            const uint32_t* __restrict__ exp_words, int row0, int nrows,
@@ -1553,11 +1483,16 @@ namespace {
 struct Lens {
   uint64_t n, lz, la, lzx, lab, labqm, lq1, lt1, l2a, l2b, l2, lzw, l3, lz1, lt4, lnum, lq, ltx, lr3, lrx, lw, lwq,
       lzz, lwo;
+  // t_lo / t_mid / t_hi = poly_slice(t_x, ...) at part = n + 2 (src/plonk.h:513-519): the slices' own
+  // lengths, 0 when t_x does not reach them (a commitment row or a byte count takes at least 1)
+  uint64_t part, ltlo, ltmid, lthi;
 };
 Lens lens_for(uint64_t n, uint64_t lz) {
   Lens L{};
   L.n = n;
   L.lz = lz;
+  // la <= lzx <= la + 1 for every (n, lz): n <= lz + 1 gives la = lz + 1 and lzx = la + 1, n >= lz + 2
+  // gives both n (rounds() takes prep_kernel, written for such lengths, without testing it)
   L.la = std::max<uint64_t>(lz + 1, n);          // a_x, b_x, c_x
   L.lzx = std::max<uint64_t>(lz + 2, n);         // z_x
   L.lab = 2 * L.la - 1;                          // a_x b_x
@@ -1576,9 +1511,11 @@ Lens lens_for(uint64_t n, uint64_t lz) {
   L.ltx = L.lnum >= lz ? L.lnum - lz + 1 : 1;
   L.lr3 = L.lzx + n - 1;                         // z_x * (s_sigma_3 scaled)
   L.lrx = std::max(std::max<uint64_t>(n, L.lzx), L.lr3);
-  const uint64_t p = n + 2;
-  const uint64_t lhi = L.ltx > 2 * p ? L.ltx - 2 * p : 1;
-  L.lw = std::max(std::max<uint64_t>(p, lhi), std::max(L.lrx, std::max<uint64_t>(L.la, n)));
+  const uint64_t p = L.part = n + 2;
+  L.ltlo = std::min(p, L.ltx);
+  L.ltmid = L.ltx > p ? std::min(p, L.ltx - p) : 0;
+  L.lthi = L.ltx > 2 * p ? L.ltx - 2 * p : 0;
+  L.lw = std::max(std::max(p, L.lthi), std::max(L.lrx, std::max<uint64_t>(L.la, n)));
   L.lwq = L.lw >= 2 ? L.lw - 1 : 1;
   L.lzz = L.lzx;
   L.lwo = L.lzz >= 2 ? L.lzz - 1 : 1;
@@ -1593,14 +1530,13 @@ Lens lens_for(uint64_t n, uint64_t lz) {
 // poly_scale chains) are not counted: a lower bound on any implementation's traffic.
 uint64_t alg_bytes_for(const Lens& L) {
   auto pm = [](uint64_t a, uint64_t b) { return a + b + (a + b - 1); };
-  const uint64_t n = L.n, lz = L.lz, part = n + 2;
-  const uint64_t lmid = L.ltx > part ? std::min<uint64_t>(part, L.ltx - part) : 1;
-  const uint64_t lhi = L.ltx > 2 * part ? L.ltx - 2 * part : 1;
+  const uint64_t n = L.n, lz = L.lz;
+  const uint64_t lmid = std::max<uint64_t>(L.ltmid, 1), lhi = std::max<uint64_t>(L.lthi, 1);
   uint64_t s = 3 * pm(2, lz) + pm(3, lz);                                        // rounds 1-2 blindings
   s += pm(L.la, L.la) + pm(L.lab, n) + 3 * pm(L.la, n);                          // a b, (a b) q_m, a q_l ..
   s += 2 * pm(L.la, L.la) + 2 * pm(L.l2a, L.la) + pm(L.l2b, L.lzx) + pm(L.l2b, L.lzw);   // t_2, t_3
   s += pm(L.lz1, n) + pm(L.lzx, n);                                              // Z1 l_1, z_x s_sigma_3
-  s += 4 * (3 * L.la + L.lzx + std::min<uint64_t>(part, L.ltx) + lmid + lhi + L.lwq + L.lwo);   // commits
+  s += 4 * (3 * L.la + L.lzx + L.ltlo + lmid + lhi + L.lwq + L.lwo);   // commits
   s += (L.lnum + lz + L.ltx + (lz - 1)) + (L.lw + 2 + L.lwq + 1) + (L.lzz + 2 + L.lwo + 1);     // divisions
   s += 3 * L.la + 2 * n + L.ltx + L.lzw + n + L.lrx;                             // evaluations at z
   return s;
@@ -1666,36 +1602,6 @@ int lincomb_batch(plk_prover* P, std::initializer_list<LcArgs> list) {
   return PLK_OK;
 }
 
-int lincomb(plk_prover* P, std::initializer_list<std::pair<const uint8_t*, uint64_t>> terms,
-            std::initializer_list<int> slots, int c0, int c1, int scale, int twist, uint8_t* out, uint64_t out_len) {
-  LcArgs a{};
-  int t = 0;
-  for (const auto& pr : terms) { a.p[t] = pr.first; a.len[t] = pr.second; t++; }
-  int s = 0;
-  for (int sl : slots) a.slot[s++] = sl;
-  if (t != s || t > LC_MAX) { plk_set_error("lincomb: %d terms / %d slots", t, s); return PLK_ERR_ARG; }
-  a.nt = t;
-  a.c0 = c0;
-  a.c1 = c1;
-  a.scale = scale;
-  a.twist = twist;
-  a.out = out;
-  a.out_len = out_len;
-  bool vec = ((uintptr_t)out % 16) == 0;
-  for (int i = 0; i < t; i++) vec = vec && ((uintptr_t)a.p[i] % 16) == 0;
-  if (vec) {
-    const uint64_t blocks = std::min<uint64_t>((out_len + 4095) / 4096, 2048);
-    hipLaunchKernelGGL(lincomb16_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(256), 0, P->st, a,
-                       P->d_S);
-  } else {
-    const uint64_t blocks = std::min<uint64_t>((out_len + 255) / 256, 2048);
-    hipLaunchKernelGGL(lincomb_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(256), 0, P->st, a,
-                       P->d_S);
-  }
-  PLK_HIP(hipGetLastError());
-  return PLK_OK;
-}
-
 // one evaluation of a batch, or (join) one more row of the previous entry's evaluation
 struct EvSpec {
   const uint8_t* p;
@@ -1730,7 +1636,7 @@ EvArgs make_evargs(plk_prover* P, const std::vector<EvSpec>& ev, int post, bool*
     ok = ok && (t.col < 0 || col >= 0);
     const bool grouped = t.join || (q + 1 < ev.size() && ev[q + 1].join);
     int parts = 1;
-    if (!grouped && PLK_EV_SPLIT && vec && base >= 4096 && len >= 2 * base)
+    if (!grouped && vec && base >= 4096 && len >= 2 * base)
       parts = (int)std::min<uint64_t>((len + base / 2) / base, (uint64_t)(1 + spare));
     spare -= parts - 1;
     uint64_t chunk = ((len + parts - 1) / parts + 15) / 16 * 16;
@@ -1760,19 +1666,10 @@ EvArgs make_evargs(plk_prover* P, const std::vector<EvSpec>& ev, int post, bool*
   if (agg_ok) *agg_ok = ok && agg;
   return a;
 }
-EvArgs make_evargs(plk_prover* P, std::initializer_list<std::tuple<const uint8_t*, uint64_t, int, int>> ev, int post) {
-  std::vector<EvSpec> v;
-  for (const auto& t : ev) v.push_back(EvSpec{std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t)});
-  return make_evargs(P, v, post);
-}
 int evals_launch(plk_prover* P, const EvArgs& a) {
   hipLaunchKernelGGL(eval_kernel, dim3(EV_BLOCKS, a.nr), dim3(256), 0, P->st, a, P->d_S, P->d_tick, P->d_stat);
   PLK_HIP(hipGetLastError());
   return PLK_OK;
-}
-int evals(plk_prover* P, std::initializer_list<std::tuple<const uint8_t*, uint64_t, int, int>> ev, int post) {
-  const EvArgs a = make_evargs(P, ev, post);
-  return evals_launch(P, a);
 }
 
 int pmul(plk_prover* P, const uint8_t* a, uint64_t la, const uint8_t* b, uint64_t lb, uint8_t* out) {
@@ -1934,8 +1831,8 @@ int create_on(const plk_plonk_desc_t* d, int dev, plk_prover_t** out) {
   // commitments: a b c z t_lo t_mid t_hi w_z w_zw
   // committed lengths: a b c z (la, lzx), t_lo / t_mid / t_hi (poly_slice of t_x at part = n + 2:
   // <= part, <= part, ltx - 2 part), w_z, w_zw (lwq, lwo) -- t_x itself is never committed
-  const uint64_t lthi = L.ltx > 2 * (n + 2) ? L.ltx - 2 * (n + 2) : 1;
-  P->cmax = std::max(std::max(L.la, L.lzx), std::max(std::max<uint64_t>(n + 2, lthi), std::max(L.lwq, L.lwo)));
+  const uint64_t lthi = std::max<uint64_t>(L.lthi, 1);
+  P->cmax = std::max(std::max(L.la, L.lzx), std::max(std::max(L.part, lthi), std::max(L.lwq, L.lwo)));
   P->cstride = (P->cmax + 15) & ~(size_t)15;
   // poly_mul workspace: the largest batch of round 3 (rounds()), or a single product
   size_t ws = 0;
@@ -2081,12 +1978,9 @@ struct RoundsMode {
 // the 9 commitment rows' MSM lengths: a b c z t_lo t_mid t_hi w_z w_zw (the arena rows' order),
 // each its polynomial's upper-bound length (P->cmax's terms), at most the SRS length
 MsmRowLens msm_row_lens(const plk_prover* P, const Lens& L) {
-  const uint64_t part = L.n + 2, lthi = L.ltx > 2 * part ? L.ltx - 2 * part : 1;
-  const uint64_t len[9] = {L.la, L.la, L.la, L.lzx, part, part, lthi, L.lwq, L.lwo};
+  const uint64_t len[9] = {L.la, L.la, L.la, L.lzx, L.part, L.part, std::max<uint64_t>(L.lthi, 1), L.lwq, L.lwo};
   MsmRowLens r{};
-  for (int i = 0; i < 9; i++)
-    r.n[i] = PLK_MSM_ROW_LENS ? std::min<uint64_t>(std::min<uint64_t>(len[i], P->cmax), P->srs_len)
-                              : std::min<uint64_t>(P->cmax, P->srs_len);
+  for (int i = 0; i < 9; i++) r.n[i] = std::min<uint64_t>(std::min<uint64_t>(len[i], P->cmax), P->srs_len);
   return r;
 }
 
@@ -2123,9 +2017,8 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
   // status: stage-A words (gate/copy/acc) are owned by the circuit path; reset the rest
   // (the aligned path's prep_kernel stores the scalar file and clears the status words itself)
   const uint8_t* ins[8] = {P->d_zh, pl[0], pl[1], pl[2], pl[11], pl[8], pl[9], pl[10]};
-  bool aligned = true;
-  for (const uint8_t* q : ins) aligned = aligned && ((uintptr_t)q % 16) == 0;
-  const bool prep = aligned && L.la <= L.lzx && L.lzx <= L.la + 1;
+  bool prep = true;
+  for (const uint8_t* q : ins) prep = prep && ((uintptr_t)q % 16) == 0;
   if (!prep) {
     hipLaunchKernelGGL(scalars_init_kernel, dim3(1), dim3(NSLOT), 0, P->st, sf, P->d_S, P->d_stat, 0, (int)ST_GATE);
     PLK_HIP(hipGetLastError());
@@ -2173,7 +2066,7 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
                           make_lc({{P->blC, L.lz + 1}, {FC, n}}, {S_ONE, S_ONE}, -1, -1, S_ONE, -1, cC, L.la)}));
     // ---- round 2: z_x = (b9 + b8 x + b7 x^2) Z_H + acc_x  (1 poly_mul)
     RC(pmul(P, dS + P_BLZ, 3, P->d_zh, L.lz, P->zB));
-    RC(lincomb(P, {{P->zB, L.lz + 2}, {ACC, n}}, {S_ONE, S_ONE}, -1, -1, S_ONE, -1, cZ, L.lzx));
+    RC(lincomb_batch(P, {make_lc({{P->zB, L.lz + 2}, {ACC, n}}, {S_ONE, S_ONE}, -1, -1, S_ONE, -1, cZ, L.lzx)}));
     // ---- round 3: t(x) numerator (12 poly_mul), src/plonk.h:386-503.  The linear factors
     // first, then the products in two batches of independent ones (one launch per NTT pass for
     // a whole batch): 10 at 2n (incl. the 17th and the re-associated C2 z, C3 z(omega x)), 3 at 4n.
@@ -2281,9 +2174,7 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
     if (md.ext && e) PLK_HIP(hipStreamWaitEvent(P->st, e, 0));
   // t(x) = numerator / Z_H; t_lo / t_mid / t_hi = poly_slice(t_x, ...) with part n + 2
   // (src/plonk.h:494-519)
-  const uint64_t part = n + 2;
-  const uint64_t lmid = L.ltx > part ? std::min<uint64_t>(part, L.ltx - part) : 0;
-  const uint64_t lhi = L.ltx > 2 * part ? L.ltx - 2 * part : 0;
+  const uint64_t part = L.part;
   // (the sums in AQL / T2 stand for their members' terms)
   LcArgs num = P->lin_sum
                    ? make_lc({{P->ABQM, L.labqm}, {P->AQL, L.lq1}, {QC, n}, {T2, L.l2}, {T3, L.l3}, {P->T4, L.lt4}},
@@ -2307,7 +2198,7 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
   for (int t = 0; t < num.nt; t++) fused = fused && (uintptr_t)num.p[t] % 4 == 0;
   if (fused) {
     const uint64_t m = P->zh_len - 1, ql = L.ltx, nb = (m / 4 + 255) / 256;
-    const Slices3 sl{{cTlo, cTmid, cThi}, {std::min<uint64_t>(part, L.ltx), lmid, lhi}, part};
+    const Slices3 sl{{cTlo, cTmid, cThi}, {L.ltlo, L.ltmid, L.lthi}, part};
     const uint64_t cq = ql ? (ql - 1) / m : 0, cr = ql ? (ql - 1) % m : 0;
 #define PLK_NUMDIV(NT_, K_)                                                                                      \
   hipLaunchKernelGGL((numdiv_kernel<NT_, K_>), dim3((unsigned)nb), dim3(256), 0, P->st, num, dS, m, P->zh_lead, P->zh_c, \
@@ -2326,8 +2217,7 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
   } else {
     RC(lincomb_batch(P, {num}));
     RC(divide_zh(P, P->NUM, L.lnum, P->TX, L.ltx, P->d_stat + ST_REM_T));
-    const Copy3 c{{P->TX, P->TX + part, P->TX + 2 * part}, {cTlo, cTmid, cThi},
-                  {std::min<uint64_t>(part, L.ltx), lmid, lhi}};
+    const Copy3 c{{P->TX, P->TX + part, P->TX + 2 * part}, {cTlo, cTmid, cThi}, {L.ltlo, L.ltmid, L.lthi}};
     const uint64_t blocks = std::min<uint64_t>((c.len[0] + 255) / 256, 2048);
     hipLaunchKernelGGL(copy3_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1), 3), dim3(256), 0, P->st, c);
     PLK_HIP(hipGetLastError());
@@ -2352,9 +2242,8 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
   // q_o z_x P3 a_x b_x c_x s_sigma_1 s_sigma_2; column 14 = z(omega x) at z = z_x at z omega
   enum { AC_TLO, AC_TMID, AC_THI, AC_QM, AC_QL, AC_QR, AC_QO, AC_ZX, AC_P3, AC_A, AC_B, AC_C, AC_S1, AC_S2, AC_ZW };
   LcArgs* const num5 = nb5.lcs.a;   // [0]: W, [1]: ZZ
-  num5[0] = make_lc({{cTlo, std::min<uint64_t>(part, L.ltx)}, {cTmid, lmid}, {cThi, lhi}, {QM, n}, {QL, n},
-                     {QR, n}, {QO, n}, {cZ, L.lzx}, {P->P3, L.lr3}, {cA, L.la}, {cB, L.la}, {cC, L.la}, {S1, n},
-                     {S2, n}},
+  num5[0] = make_lc({{cTlo, L.ltlo}, {cTmid, L.ltmid}, {cThi, L.lthi}, {QM, n}, {QL, n}, {QR, n}, {QO, n},
+                     {cZ, L.lzx}, {P->P3, L.lr3}, {cA, L.la}, {cB, L.la}, {cC, L.la}, {S1, n}, {S2, n}},
                     {S_ONE, S_ZN2, S_Z2N4, S_VAB, S_VAZ, S_VBZ, S_VCZ, S_VR24, S_VR3B, S_V2, S_V3, S_V4, S_V5,
                      S_V6},
                     S_W0, -1, S_ONE, -1, P->W, L.lw);
@@ -2373,8 +2262,8 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
     ea = make_evargs(P,
                      {{cA, L.la, S_Z, S_AZ, AC_A}, {cB, L.la, S_Z, S_BZ, AC_B}, {cC, L.la, S_Z, S_CZ, AC_C},
                       {S1, n, S_Z, S_S1Z, AC_S1}, {S2, n, S_Z, S_S2Z, AC_S2},
-                      {cTlo, std::min<uint64_t>(part, L.ltx), S_Z, S_TZ, AC_TLO},
-                      {cTmid, lmid, S_Z, S_TZ, AC_TMID, m1, true}, {cThi, lhi, S_Z, S_TZ, AC_THI, m2, true},
+                      {cTlo, L.ltlo, S_Z, S_TZ, AC_TLO},
+                      {cTmid, L.ltmid, S_Z, S_TZ, AC_TMID, m1, true}, {cThi, L.lthi, S_Z, S_TZ, AC_THI, m2, true},
                       {P->ZW, L.lzw, S_Z, S_ZWZ, AC_ZW}, {L1, n, S_Z, S_L1Z},
                       {QM, n, S_Z, S_QMZ, AC_QM}, {QL, n, S_Z, S_QLZ, AC_QL}, {QR, n, S_Z, S_QRZ, AC_QR},
                       {QO, n, S_Z, S_QOZ, AC_QO}, {cZ, L.lzx, S_Z, S_ZXZ, AC_ZX}, {P->P3, L.lr3, S_Z, S_P3Z, AC_P3}},
@@ -2404,17 +2293,13 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
                    fuse ? &nb5 : nullptr, early ? &em : nullptr));
   // ---- trimmed lengths for the reference's exits: computed by the packing kernel after the MSM
   TrimArgs trims{};
-  int ntrims = 0;
+  int ntrims = 10;
   {
-    TrimArgs t{};
     const uint8_t* cps[9] = {cA, cB, cC, cZ, cTlo, cTmid, cThi, cWz, cWzw};
-    const uint64_t ub[9] = {L.la, L.la, L.la, L.lzx, std::min<uint64_t>(part, L.ltx), lmid, lhi, L.lwq, L.lwo};
-    for (int i = 0; i < 9; i++) { t.p[i] = cps[i]; t.len[i] = std::max<uint64_t>(ub[i], 1); t.dst[i] = ST_LEN0 + i; }
-    t.p[9] = P->TX; t.len[9] = L.ltx; t.dst[9] = ST_TXLEN;
-    int nt = 10;
-    if (P->rem_blocks) { t.p[10] = P->d_rem; t.len[10] = P->rem_blocks; t.dst[10] = ST_REM_T | TRIM_ANY; nt = 11; }
-    trims = t;
-    ntrims = nt;
+    const uint64_t ub[9] = {L.la, L.la, L.la, L.lzx, L.ltlo, L.ltmid, L.lthi, L.lwq, L.lwo};
+    for (int i = 0; i < 9; i++) { trims.p[i] = cps[i]; trims.len[i] = std::max<uint64_t>(ub[i], 1); trims.dst[i] = ST_LEN0 + i; }
+    trims.p[9] = P->TX; trims.len[9] = L.ltx; trims.dst[9] = ST_TXLEN;
+    if (P->rem_blocks) { trims.p[10] = P->d_rem; trims.len[10] = P->rem_blocks; trims.dst[10] = ST_REM_T | TRIM_ANY; ntrims = 11; }
   }
   // ---- the 9 commitments: one batched MSM over the arena (srs_eval_at_s, src/srs.h:53-68)
   const uint64_t nm = std::min<uint64_t>(P->cmax, P->srs_len);
@@ -2422,11 +2307,11 @@ int rounds(plk_prover* P, const uint8_t* const* pl, const uint8_t chal[5], const
   if (!P->srs_irregular && plk_opt(PLK_OPT_PROVE_SRS_LOGS) && plk_opt(PLK_OPT_PROVE_PACK_FUSE)) {
     // commitments + trimmed lengths + packing in one launch (commit_pack_kernel)
     const int row0 = P->early_rows == 7 ? 7 : 0, nrows = 9 - row0;
-    // (blocks per row: one 16-point group per thread up to PLK_CP_BX blocks)
-    const uint64_t bx = std::max<uint64_t>(std::min<uint64_t>(PLK_CP_BX, std::max<uint64_t>(1, ((nm >> 4) + CP_T - 1) / CP_T)),
+    // (blocks per row: one 16-point group per thread up to CP_BX blocks)
+    const uint64_t bx = std::max<uint64_t>(std::min<uint64_t>(CP_BX, std::max<uint64_t>(1, ((nm >> 4) + CP_T - 1) / CP_T)),
                                            (uint64_t)ntrims);
     hipLaunchKernelGGL(commit_pack_kernel, dim3((unsigned)bx, nrows + 1), dim3(CP_T), 0, P->st, P->d_srs_log, P->arena,
-                       (uint64_t)P->cstride, msm_row_lens(P, L), P->d_res, P->exp_words, row0, nrows, trims, ntrims, P->d_S, P->d_stat,
+                       (uint64_t)P->cstride, rl, P->d_res, P->exp_words, row0, nrows, trims, ntrims, P->d_S, P->d_stat,
                        P->d_res_host, ++P->seq, P->d_done);
     PLK_HIP(hipGetLastError());
     PLK_MARK(7);
@@ -2468,7 +2353,10 @@ int check_status(const plk_prover* P, const uint32_t* st, int strict, int circui
   return PLK_OK;
 }
 
-int finish(plk_prover* P, int strict, int circuit, uint8_t proof[34]) {
+// The end of every proving call.  erc: what enqueueing the rounds returned; a failed enqueue waits
+// for what did reach the stream and returns its code.
+int finish(plk_prover* P, int erc, int strict, int circuit, uint8_t proof[34]) {
+  if (erc) { (void)hipStreamSynchronize(P->st); return erc; }
   // trim_pack_kernel wrote P->h_res (mapped pinned) and then this call's completion word: poll it
   // (the stream's own completion is noticed later than the word; PLK_OPT_PROVE_SYNC = 1 waits for
   // the stream instead).  A failed launch never writes it: the stream is queried now and then.
@@ -2496,6 +2384,25 @@ int finish(plk_prover* P, int strict, int circuit, uint8_t proof[34]) {
   const int rc = check_status(P, hs, strict, circuit);
   if (rc) return rc;
   if (proof) memcpy(proof, P->h_res, 34);
+  return PLK_OK;
+}
+
+// The entry points' argument check: the handle and the arrays (rest: the call's other required
+// pointers), then every polynomial non-NULL.  multi (plk_prover_rounds_multi_dev): d_polys holds
+// `sets` sets of 13, one per device of the prover.
+int check_poly_args(const char* fn, const plk_prover* P, const uint8_t* const* d_polys, bool rest, bool multi = false,
+                    int sets = 1) {
+  if (!P || !d_polys || !rest) { plk_set_error("%s: NULL argument", fn); return PLK_ERR_ARG; }
+  if (multi && sets != 1 + P->nhelp) {
+    plk_set_error("%s: %d input sets for 1 + %d devices", fn, sets, P->nhelp);
+    return PLK_ERR_ARG;
+  }
+  for (int i = 0; i < 13 * sets; i++) {
+    if (d_polys[i]) continue;
+    if (multi) plk_set_error("%s: polynomial %d of set %d is NULL", fn, i % 13, i / 13);
+    else plk_set_error("%s: polynomial %d is NULL", fn, i);
+    return PLK_ERR_ARG;
+  }
   return PLK_OK;
 }
 
@@ -2606,32 +2513,28 @@ extern "C" {
 
 int plk_prover_rounds_dev(plk_prover_t* P, const uint8_t* const d_polys[13], const uint8_t chal[5],
                           const uint8_t rand9[9], int flags, uint8_t proof[34]) {
-  if (!P || !d_polys || !chal || !rand9) { plk_set_error("plk_prover_rounds_dev: NULL argument"); return PLK_ERR_ARG; }
-  for (int i = 0; i < 13; i++)
-    if (!d_polys[i]) { plk_set_error("plk_prover_rounds_dev: polynomial %d is NULL", i); return PLK_ERR_ARG; }
+  int rc = check_poly_args("plk_prover_rounds_dev", P, d_polys, chal && rand9);
+  if (rc) return rc;
   const bool pre = (flags & PLK_PROVE_PREPROCESSED) != 0;
   PROVER_ON_DEVICE(P);
-  int rc = P->nhelp ? rounds_split(P, d_polys, nullptr, chal, rand9, pre) : rounds(P, d_polys, chal, rand9, pre);
-  if (rc) { (void)hipStreamSynchronize(P->st); return rc; }
-  return finish(P, (flags & PLK_PROVE_STRICT) != 0, 0, proof);
+  rc = P->nhelp ? rounds_split(P, d_polys, nullptr, chal, rand9, pre) : rounds(P, d_polys, chal, rand9, pre);
+  return finish(P, rc, (flags & PLK_PROVE_STRICT) != 0, 0, proof);
 }
 
 int plk_prover_profile_dev(plk_prover_t* P, const uint8_t* const d_polys[13], const uint8_t chal[5],
                            const uint8_t rand9[9], int flags, uint8_t proof[34], double ms[4]) {
-  if (!P || !d_polys || !chal || !rand9 || !ms) { plk_set_error("plk_prover_profile_dev: NULL argument"); return PLK_ERR_ARG; }
-  for (int i = 0; i < 13; i++)
-    if (!d_polys[i]) { plk_set_error("plk_prover_profile_dev: polynomial %d is NULL", i); return PLK_ERR_ARG; }
+  int rc = check_poly_args("plk_prover_profile_dev", P, d_polys, chal && rand9 && ms);
+  if (rc) return rc;
   if (P->nhelp) { plk_set_error("plk_prover_profile_dev: a prover with helpers attached"); return PLK_ERR_ARG; }
   PROVER_ON_DEVICE(P);
   for (hipEvent_t& e : P->tev)
     if (!e) PLK_HIP(hipEventCreate(&e));
   PLK_HIP(hipEventRecord(P->tev[0], P->st));
   P->tev_on = true;
-  int rc = rounds(P, d_polys, chal, rand9, (flags & PLK_PROVE_PREPROCESSED) != 0);
+  rc = rounds(P, d_polys, chal, rand9, (flags & PLK_PROVE_PREPROCESSED) != 0);
   P->tev_on = false;
   if (!rc) rc = hipEventRecord(P->tev[5], P->st) == hipSuccess ? PLK_OK : PLK_ERR_HIP;
-  if (rc) { (void)hipStreamSynchronize(P->st); return rc; }
-  if ((rc = finish(P, (flags & PLK_PROVE_STRICT) != 0, 0, proof))) return rc;
+  if ((rc = finish(P, rc, (flags & PLK_PROVE_STRICT) != 0, 0, proof))) return rc;
   PLK_HIP(hipEventSynchronize(P->tev[5]));
   float t[3];
   PLK_HIP(hipEventElapsedTime(&t[0], P->tev[0], P->tev[5]));
@@ -2646,15 +2549,14 @@ int plk_prover_profile_dev(plk_prover_t* P, const uint8_t* const d_polys[13], co
 
 int plk_prover_launches(plk_prover_t* P, const uint8_t* const d_polys[13], const uint8_t chal[5], const uint8_t rand9[9],
                         int flags, int* kernels, int* other_nodes) {
-  if (!P || !d_polys || !chal || !rand9 || !kernels) { plk_set_error("plk_prover_launches: NULL argument"); return PLK_ERR_ARG; }
-  for (int i = 0; i < 13; i++)
-    if (!d_polys[i]) { plk_set_error("plk_prover_launches: polynomial %d is NULL", i); return PLK_ERR_ARG; }
+  int rc = check_poly_args("plk_prover_launches", P, d_polys, chal && rand9 && kernels);
+  if (rc) return rc;
   if (P->nhelp) { plk_set_error("plk_prover_launches: a prover with helpers attached"); return PLK_ERR_ARG; }
   PROVER_ON_DEVICE(P);
   PLK_HIP(hipStreamSynchronize(P->st));
   const uint32_t seq = P->seq;
   PLK_HIP(hipStreamBeginCapture(P->st, hipStreamCaptureModeThreadLocal));
-  int rc = rounds(P, d_polys, chal, rand9, (flags & PLK_PROVE_PREPROCESSED) != 0);
+  rc = rounds(P, d_polys, chal, rand9, (flags & PLK_PROVE_PREPROCESSED) != 0);
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(P->st, &g);
   P->seq = seq;   // (nothing ran: the next call's completion word is unchanged)
@@ -2764,18 +2666,12 @@ int plk_prover_helpers(const plk_prover_t* P) { return P ? P->nhelp : 0; }
 
 int plk_prover_rounds_multi_dev(plk_prover_t* P, const uint8_t* const* d_polys, int ndev, const uint8_t chal[5],
                                 const uint8_t rand9[9], int flags, uint8_t proof[34]) {
-  if (!P || !d_polys || !chal || !rand9) { plk_set_error("plk_prover_rounds_multi_dev: NULL argument"); return PLK_ERR_ARG; }
-  if (ndev != 1 + P->nhelp) {
-    plk_set_error("plk_prover_rounds_multi_dev: %d input sets for 1 + %d devices", ndev, P->nhelp);
-    return PLK_ERR_ARG;
-  }
-  for (int i = 0; i < 13 * ndev; i++)
-    if (!d_polys[i]) { plk_set_error("plk_prover_rounds_multi_dev: polynomial %d of set %d is NULL", i % 13, i / 13); return PLK_ERR_ARG; }
+  int rc = check_poly_args("plk_prover_rounds_multi_dev", P, d_polys, chal && rand9, true, ndev);
+  if (rc) return rc;
   const bool pre = (flags & PLK_PROVE_PREPROCESSED) != 0;
   PROVER_ON_DEVICE(P);
-  int rc = P->nhelp ? rounds_split(P, d_polys, d_polys, chal, rand9, pre) : rounds(P, d_polys, chal, rand9, pre);
-  if (rc) { (void)hipStreamSynchronize(P->st); return rc; }
-  return finish(P, (flags & PLK_PROVE_STRICT) != 0, 0, proof);
+  rc = P->nhelp ? rounds_split(P, d_polys, d_polys, chal, rand9, pre) : rounds(P, d_polys, chal, rand9, pre);
+  return finish(P, rc, (flags & PLK_PROVE_STRICT) != 0, 0, proof);
 }
 
 size_t plk_prover_chain_bytes(const plk_prover_t* P, int which) {
@@ -2787,9 +2683,8 @@ size_t plk_prover_chain_bytes(const plk_prover_t* P, int which) {
 namespace {
 int check_chain_args(const char* fn, const plk_prover_t* P, const uint8_t* const* d_polys, const uint8_t* chal,
                      const uint8_t* rand9, int which, const void* t2, const void* t3) {
-  if (!P || !d_polys || !chal || !rand9) { plk_set_error("%s: NULL argument", fn); return PLK_ERR_ARG; }
-  for (int i = 0; i < 13; i++)
-    if (!d_polys[i]) { plk_set_error("%s: polynomial %d is NULL", fn, i); return PLK_ERR_ARG; }
+  const int rc = check_poly_args(fn, P, d_polys, chal && rand9);
+  if (rc) return rc;
   if (which & ~(PLK_CHAIN_T2 | PLK_CHAIN_T3)) { plk_set_error("%s: bad chain mask %d", fn, which); return PLK_ERR_ARG; }
   if (((which & PLK_CHAIN_T2) && !t2) || ((which & PLK_CHAIN_T3) && !t3)) {
     plk_set_error("%s: NULL chain buffer", fn);
@@ -2850,8 +2745,7 @@ int plk_prover_rounds_ext_dev(plk_prover_t* P, const uint8_t* const d_polys[13],
     md.ready[0] = P->ev;
   }
   rc = rounds(P, d_polys, chal, rand9, (flags & PLK_PROVE_PREPROCESSED) != 0, md);
-  if (rc) { (void)hipStreamSynchronize(P->st); return rc; }
-  return finish(P, (flags & PLK_PROVE_STRICT) != 0, 0, proof);
+  return finish(P, rc, (flags & PLK_PROVE_STRICT) != 0, 0, proof);
 }
 
 int plk_prover_preprocess(plk_prover_t* P, const uint8_t* const d_polys[13]) {
@@ -2950,15 +2844,14 @@ int plk_prover_prove(plk_prover_t* P, const plk_circuit_t* c, const uint8_t chal
   PLK_HIP(hipGetLastError());
   // acc_x(omega^n) must be 1 (src/plonk.h:366-368): evaluated straight into its status word
   {
-    const int erc = evals(P, {{P->d_polys[11], n, S_ACCW + 1, S_ACCW}}, EV_POST_ACC);
+    const int erc = evals_launch(P, make_evargs(P, {{P->d_polys[11], n, S_ACCW + 1, S_ACCW}}, EV_POST_ACC));
     if (erc) { (void)hipStreamSynchronize(P->st); return erc; }
   }
 
   const uint8_t* pl[13];
   for (int i = 0; i < 13; i++) pl[i] = P->d_polys[i];
-  int rc = P->nhelp ? rounds_split(P, pl, nullptr, chal, rand9, false) : rounds(P, pl, chal, rand9);
-  if (rc) { (void)hipStreamSynchronize(P->st); return rc; }
-  return finish(P, 1, 1, proof);
+  const int rc = P->nhelp ? rounds_split(P, pl, nullptr, chal, rand9, false) : rounds(P, pl, chal, rand9);
+  return finish(P, rc, 1, 1, proof);
 }
 
 }  // extern "C"

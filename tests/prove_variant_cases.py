@@ -1,5 +1,5 @@
 """Which kernels the device prover takes for one placement of the caller's 13 polynomials, restated
-from plonk.c_amd/csrc/prove.hip (rounds(), lincomb_batch, lincomb, make_evargs, divide_zh,
+from plonk.c_amd/csrc/prove.hip (rounds(), lincomb_batch, make_evargs, divide_zh,
 divide_linear), and the placements and sizes that tests/test_prove_variants_gpu.py runs.
 tests/test_prove_variants_cpu.py checks that the lists reach every variant; the GPU file checks
 the counted launches (plk_prover_launches) against launch_delta.
@@ -9,11 +9,11 @@ n % 16 (binomial Z_H = x^n - 1 of n + 1 coefficients, one device, no helpers; th
 buffers -- Z_H's copy, the commitment arena, every intermediate -- are 16-byte aligned and padded):
 
   prep    rounds 1-3 preparation in one launch (prep_kernel): f_a f_b f_c acc_x s_sigma_1..3 all
-          16-byte aligned (the length condition la <= lzx <= la + 1 beside it is n + 2 <= n + 3 <=
-          n + 3 for this Z_H: it holds at every n).  Else scalars_init_kernel, 4 blinding products
+          16-byte aligned (the lengths satisfy la <= lzx <= la + 1 at every n and Z_H, n + 2 <= n + 3
+          <= n + 3 for this Z_H: lens_for).  Else scalars_init_kernel, 4 blinding products
           (direct kernel, one launch each), a lincomb_batch of 3 (one lincomb16_batch launch when
-          f_a f_b f_c are aligned, else 3 lincomb_kernel), one lincomb (acc_x: one launch either way),
-          a lincomb_batch of 8 (one launch when s_sigma_1..3 are aligned, else 8).
+          f_a f_b f_c are aligned, else 3 lincomb_kernel), a lincomb_batch of 1 (acc_x: one launch
+          either way), a lincomb_batch of 8 (one launch when s_sigma_1..3 are aligned, else 8).
   numdiv  t(x)'s numerator and its division by Z_H in one launch (numdiv_kernel): n % 4 == 0 and q_c
           4-byte aligned.  Else lincomb_batch({num}) (one launch either way), divide_zh
           (divide_binomial4_kernel when n % 4 == 0, else divide_binomial_kernel: one launch),
