@@ -594,6 +594,85 @@ int plk_kzg_verify_fold_batch_dev(const plk_kzg_vk_t *vk /* HOST */, int k, cons
                                   const uint8_t *d_weights, const uint8_t *d_ys, const uint8_t *d_zs,
                                   const uint8_t *d_proofs3, size_t n, uint8_t *d_ok, void *stream);
 
+/* ---- KZG multi-point openings: each polynomial at its own point set, two G1s ---------------
+ * The second scheme of Boneh-Drake-Fisch-Gabizon over this library's key ([1]_2 and [s]_2 only): a group
+ * of k polynomials p_0 .. p_{k-1}, 1 <= k <= PLK_KZG_MULTI_MAX, polynomial i opened at every point of its
+ * own set S_i, costs two G1 elements in all and is checked with two pairings.  A set is a uint32_t mask,
+ * bit a set <=> a in S_i, bits 0 .. 16 only, 1 .. PLK_KZG_MULTI_POINTS bits set: no repeated points, and
+ * the order of the points is ascending.  The weights w_i and the challenge u of a group are the caller's,
+ * as everywhere in this library.  With t_i = |S_i|, Z_i = plk_poly_from_roots(S_i ascending), T = the
+ * union of the S_i:
+ *     q_i = the quotient of p_i by Z_i;   h = sum_i w_i q_i over Lh = max_i max(len_i - t_i, 1) coefficients
+ *     c_i = w_i prod_{a in T \ S_i} (u - a);   c_T = prod_{a in T} (u - a)
+ *     W   = [h];   W' = the folded opening at u of (p_0 .. p_{k-1}, h) under weights (c_0 .. c_{k-1}, -c_T)
+ * sum_i c_i p_i - c_T h takes the value sum_i c_i r_i(u) at u for every u, points of T included (r_i: the
+ * remainder of p_i by Z_i), so no choice of u is special.
+ *
+ * Opening.  Grouping (start), the host / device array conventions, the records ("zeroed once, then
+ * reusable"), the device rules and the stream behaviour are those of plk_kzg_open_fold_batch(_dev); sets
+ * and weights are flat HOST arrays of npolys entries, us one HOST byte per group.  For group g the library
+ * returns exactly the bytes of this sequence of its own host calls (the specification):
+ *   ys[17 i + a] = plk_poly_eval(p_i, lens[i], a) for a in S_i, 0xFF elsewhere (all 17 bytes are written)
+ *   (q_i, .)     = plk_poly_divide_short_batch of p_i by plk_poly_from_roots(S_i ascending); len_i <= t_i: q_i = {0}
+ *   h            = plk_poly_lincomb of the q_i with scale = w_i, folded by poly_add, Lh untrimmed bytes
+ *   W            = plk_kzg_commit_batch of h trimmed
+ *   c            = plk_kzg_multi_coeffs(sets, weights, k, u)
+ *   W'           = the proof plk_kzg_open_fold_batch gives for (p_0 .. p_{k-1}, h untrimmed over Lh), weights c, z = u
+ * proofs6[6 g ..] = W then W'; _dev: record 2 g = W, record 2 g + 1 = W'; d_hs[g], where given, receives the
+ * Lh untrimmed bytes of h.  The fast path (every coefficient byte < 17, a regular SRS) never forms a q_i:
+ * by partial fractions h is a sum over the points a of T of the single-point quotients of
+ * sum_{i : a in S_i} (w_i / prod_{b in S_i, b != a} (a - b)) p_i, formed in registers: an
+ * aggregates launch when some polynomial has more than 4096 coefficients, one fused launch for ys, h and W
+ * (four whole groups per launch, larger batches in consecutive launches), then the folded opening's own
+ * launches for W', group by group.
+ *   _dev form: a group holding a coefficient byte >= 17 is left with both records irregular > 0 and its
+ *   d_ys and h unspecified; with an irregular SRS every record is flagged while ys and h stay exact.  Other
+ *   groups are unaffected.  d_work: plk_kzg_multi_workspace(lens, sets, start, ngroups) bytes, always
+ *   required (h lives there when d_hs does not ask for it), 4-byte aligned, no initialisation needed.
+ *   Host form (synchronous): such groups are recomputed by the sequence above, so the call is exact for
+ *   every coefficient byte and any SRS.
+ * Errors: a NULL handle or array, ngroups <= 0, a start that does not rise strictly from 0, a group of more
+ * than PLK_KZG_MULTI_MAX, lens[i] == 0, a mask that is 0, has a bit above 16 or has all 17 bits set, a weight
+ * or u >= 17, or a call from another device are PLK_ERR_ARG (all but the last before any device query);
+ * Lh > plk_srs_len, max(max(the longest len_i, Lh) - 1, 1) > plk_srs_len or a length beyond what one record's
+ * finish can count are PLK_ERR_RANGE; no GPU is PLK_ERR_NODEV.
+ *
+ * Verification.  k is uniform over a call; job b owns entries [k b, k (b + 1)) of commits3 / sets / weights,
+ * the 17-byte rows [17 k b, 17 k (b + 1)) of ys (only the bytes at points of the set are read), us[b] and
+ * proofs6[6 b ..] = W, W'.  With
+ *   r_i(u) = sum_{a in S_i} y_ia prod_{b in S_i, b != a} (u - b) / (a - b) mod 17   (Lagrange over S_i)
+ *   c      = plk_kzg_multi_coeffs(sets, weights, k, u)
+ * ok[b] is the ok byte of plk_kzg_verify_fold_batch with k + 1 entries: commits (C_0 .. C_{k-1}, W), weights
+ * c, ys (r_0(u) .. r_{k-1}(u), 0), z = u, proof W' -- the reference's raw formulas applied blindly, as
+ * there.  A job with an invalid G1 byte, an invalid mask, a weight or u >= 17, or a y byte >= 17 at a point
+ * of its set gets ok[b] = 2; its neighbours are unaffected.  One lane per job, no atomics, no workspace; any
+ * alignment except that d_sets is 4-byte aligned.  Errors: those of plk_kzg_verify_fold_batch with k in
+ * 1 .. PLK_KZG_MULTI_MAX.
+ * plk_kzg_multi_coeffs (host only): c[0 .. k) = c_i, c[k] = (17 - c_T) % 17; PLK_ERR_ARG for a NULL pointer, k
+ * outside 1 .. PLK_KZG_MULTI_MAX, an invalid mask, a weight or u >= 17. */
+#define PLK_KZG_MULTI_MAX 15      /* polynomials per group: the second proof folds them with h, PLK_KZG_FOLD_MAX in all */
+#define PLK_KZG_MULTI_POINTS 16   /* points per set (the divisor stays within PLK_DIV_SHORT_MAX) */
+int plk_kzg_multi_coeffs(const uint32_t *sets, const uint8_t *weights, int k, uint8_t u, uint8_t *c /* k + 1 */);
+size_t plk_kzg_multi_workspace(const size_t *lens, const uint32_t *sets, const int *start, int ngroups); /* host only; 0: bad args */
+int plk_kzg_open_multi_batch(const plk_srs_t *s, const uint8_t *const *polys, const size_t *lens,
+                             const uint32_t *sets /* npolys */, const uint8_t *weights /* npolys */,
+                             const int *start, const uint8_t *us /* ngroups */, int ngroups,
+                             uint8_t *ys /* 17 npolys */, uint8_t *proofs6 /* 6 ngroups: W, W' */);
+int plk_kzg_open_multi_batch_dev(const plk_srs_t *s, const uint8_t *const *d_polys, const size_t *lens,
+                                 const uint32_t *sets, const uint8_t *weights, const int *start,
+                                 const uint8_t *us, int ngroups, uint8_t *d_ys /* 17 npolys */,
+                                 plk_msm_result_t *d_res /* 2 ngroups: W at 2g, W' at 2g + 1 */,
+                                 uint8_t *const *d_hs /* NULL, or per group NULL / Lh bytes */,
+                                 void *d_work, void *stream);
+int plk_kzg_verify_multi_batch(const plk_kzg_vk_t *vk, int k, const uint8_t *commits3 /* 3 n k */,
+                               const uint32_t *sets /* n k */, const uint8_t *weights /* n k */,
+                               const uint8_t *ys /* 17 n k */, const uint8_t *us /* n */,
+                               const uint8_t *proofs6 /* 6 n */, size_t n, uint8_t *ok /* n */);
+int plk_kzg_verify_multi_batch_dev(const plk_kzg_vk_t *vk /* HOST */, int k, const uint8_t *d_commits3,
+                                   const uint32_t *d_sets, const uint8_t *d_weights, const uint8_t *d_ys,
+                                   const uint8_t *d_us, const uint8_t *d_proofs6, size_t n, uint8_t *d_ok,
+                                   void *stream);
+
 /* ---- device-resident prover (replaces plonk_new / plonk_prove / plonk_free,
  * src/plonk.h:53-139, 223-656, 120-139) ---------------------------------------------------
  * plk_prover_create uploads the SRS and Z_H once (the PLONK struct of plonk_new); the

@@ -29,22 +29,12 @@
 #include <algorithm>
 #include <vector>
 
+#include "kzg_multi.h"
 #include "plk_device.h"
 #include "plk_hf17.h"
 #include "plk_hostcall.h"
 #include "plk_internal.h"
 #include "plk_msm_finish.h"
-
-struct plk_srs {
-  int dev = 0;
-  size_t len = 0;
-  bool irregular = false;
-  uint8_t* d_g1 = nullptr;    // 3 len bytes (+ 16)
-  uint8_t* d_log = nullptr;   // len bytes, zero padded to a multiple of 16 (+ 16); unusable when irregular
-  uint32_t* d_flag = nullptr;
-  const uint32_t* exp_words = nullptr;
-  hipStream_t st = nullptr;   // the host-buffer forms' stream
-};
 
 namespace {
 
@@ -57,6 +47,7 @@ using hf17::load16;
 using hf17::mod17;
 using hf17::wave_suffix;
 constexpr uint64_t KZG_MAX_LEN = (8ull * 65535ull) * KZG_CHUNK;   // the finish's ticket field: blocks per record
+static_assert(KZG_MAX_LEN == PLK_KZG_RECORD_MAX_LEN, "kzg_multi.h states the same bound");
 
 struct KzgJob {
   const uint8_t* p;
@@ -855,6 +846,12 @@ int host_fold(const plk_srs* s, const uint8_t* const* polys, const size_t* lens,
 }
 
 }  // namespace
+
+int plk_kzg_fold_launch(const plk_srs* s, const uint8_t* const* d_polys, const size_t* lens, const uint8_t* weights,
+                        const int* start, const uint8_t* zs, int ngroups, uint8_t* d_ys, PlkMsmResult* d_res,
+                        uint8_t* const* d_quots, uint32_t* d_work, hipStream_t st, uint32_t row0) {
+  return launch_fold(s, d_polys, lens, weights, start, zs, ngroups, d_ys, d_res, d_quots, d_work, st, row0);
+}
 
 extern "C" {
 

@@ -15,6 +15,8 @@
 //            fixes, then pairing(L, [1]_2) == pairing(W, [s]_2), all in registers, one byte out.
 //   fold     the same check on C = the raw fold of g1_mul(C_i, w_i) over a job's k commitments and
 //            y = sum_i w_i y_i: k uniform over the launch, so every lane runs the same k steps.
+//   multi    the folded check on (C_0 .. C_{k-1}, W) with proof W' (plonkhip.h, "KZG multi-point openings"):
+//            per polynomial the Lagrange value r_i(u) over its point mask and the weight c_i, in GF(17).
 //
 // The raw G1 formulas are restated here after RawOps of msm.hip (which stays untouched); every
 // select is branch-free so the lanes of a wave do not diverge on the encodings they hold.  The
@@ -181,6 +183,22 @@ __global__ __launch_bounds__(PAIR_T) void kzg_verify_kernel(VkWords vk, const ui
   }
 }
 
+// The two steps the folded checks share.  One entry: C += g1_mul(C_i, w_i), y = hf_add(y, hf_mul(w_i, y_i))
+// (w_i, y_i < 17).  The check of kzg_verify_kernel on (C, y, W, z): 2 when the job held an invalid byte.
+__device__ __forceinline__ void fold_entry(const G1Ops& G, Pt& c, uint32_t& y, Pt ci, uint32_t wi, uint32_t yi) {
+  c = G.add(c, G.mul(ci, wi));
+  y = (y + wi * yi % HFP) % HFP;
+}
+__device__ __forceinline__ uint32_t opening_check(const G1Ops& G, const VkWords& vk, Pt c, uint32_t y, Pt w, uint32_t z,
+                                                  bool ok) {
+  const Pt g{vk.gx, vk.gy, vk.ginf};
+  Pt l = G.add(c, G.negp(G.mul(g, y)));
+  l = G.add(l, G.mul(w, z));
+  const Gt lhs = pairing(G, l, vk.h1x, vk.h1y);
+  const Gt rhs = pairing(G, w, vk.hsx, vk.hsy);
+  return !ok ? 2u : (lhs.a == rhs.a && lhs.b == rhs.b) ? 1u : 0u;
+}
+
 // Folded verification, job i: C = the fold of its k commitments under its k weights and y = the fold
 // of its k values, built with the raw g1_mul / g1_add from the identity in entry order (as
 // srs_eval_at_s folds), then the check of kzg_verify_kernel.  k is uniform over the launch, so the
@@ -193,7 +211,6 @@ __global__ __launch_bounds__(PAIR_T) void kzg_verify_fold_kernel(VkWords vk, uin
   __shared__ uint32_t invl[GFP];
   stage_inverses(invl);
   const G1Ops G{invl};
-  const Pt g{vk.gx, vk.gy, vk.ginf};
   for (size_t i = (size_t)blockIdx.x * PAIR_T + threadIdx.x; i < n; i += (size_t)gridDim.x * PAIR_T) {
     bool ok = true;
     Pt c{0, 0, 1};
@@ -206,8 +223,7 @@ __global__ __launch_bounds__(PAIR_T) void kzg_verify_fold_kernel(VkWords vk, uin
         ok = false;
         wi = yi = 0;
       }
-      c = G.add(c, G.mul(ci, wi));
-      y = (y + wi * yi % HFP) % HFP;   // hf_add(y, hf_mul(w_i, y_i))
+      fold_entry(G, c, y, ci, wi, yi);
     }
     const Pt w = load_g1(proofs + 3 * i, ok);
     uint32_t z = zs[i];
@@ -215,11 +231,74 @@ __global__ __launch_bounds__(PAIR_T) void kzg_verify_fold_kernel(VkWords vk, uin
       ok = false;
       z = 0;
     }
-    Pt l = G.add(c, G.negp(G.mul(g, y)));
-    l = G.add(l, G.mul(w, z));
-    const Gt lhs = pairing(G, l, vk.h1x, vk.h1y);
-    const Gt rhs = pairing(G, w, vk.hsx, vk.hsy);
-    okb[i] = (uint8_t)(!ok ? 2u : (lhs.a == rhs.a && lhs.b == rhs.b) ? 1u : 0u);
+    okb[i] = (uint8_t)opening_check(G, vk, c, y, w, z, ok);
+  }
+}
+
+// Multi-point verification (plonkhip.h, "KZG multi-point openings"), job i: per polynomial the Lagrange
+// value r_j(u) from the claimed evaluations over its mask and the coefficient c_j, then the folded check on
+// the k + 1 entries (C_0 .. C_{k-1}, W) with proof W'.  k is uniform over the launch; the masks are per lane.
+constexpr uint32_t SET_BITS = 17, SET_FULL = (1u << SET_BITS) - 1;
+// prod_{b in m} (x - b) mod 17 (x < 17)
+__device__ __forceinline__ uint32_t vanish_at(uint32_t m, uint32_t x) {
+  uint32_t r = 1;
+  for (uint32_t b = 0; b < SET_BITS; b++)
+    if ((m >> b) & 1u) r = hf17::mod17(r * (x + HFP - b));   // (<= 16 x 33)
+  return r;
+}
+__device__ __forceinline__ uint32_t load_set(const uint32_t* sets, size_t e, bool& ok) {
+  const uint32_t m = sets[e];
+  const bool v = m != 0 && (m & ~SET_FULL) == 0 && m != SET_FULL;
+  ok = ok && v;
+  return v ? m : 1u;
+}
+__global__ __launch_bounds__(PAIR_T) void kzg_verify_multi_kernel(VkWords vk, uint32_t k, const uint8_t* __restrict__ commits,
+                                                                 const uint32_t* __restrict__ sets,
+                                                                 const uint8_t* __restrict__ weights,
+                                                                 const uint8_t* __restrict__ ys, const uint8_t* __restrict__ us,
+                                                                 const uint8_t* __restrict__ proofs, size_t n,
+                                                                 uint8_t* __restrict__ okb) {
+  __shared__ uint32_t invl[GFP];
+  stage_inverses(invl);
+  const G1Ops G{invl};
+  for (size_t i = (size_t)blockIdx.x * PAIR_T + threadIdx.x; i < n; i += (size_t)gridDim.x * PAIR_T) {
+    bool ok = true;
+    uint32_t u = us[i];
+    if (u >= HFP) {
+      ok = false;
+      u = 0;
+    }
+    uint32_t T = 0;
+    for (uint32_t j = 0; j < k; j++) T |= load_set(sets, i * k + j, ok);
+    Pt c{0, 0, 1};
+    uint32_t y = 0;
+    for (uint32_t j = 0; j < k; j++) {
+      const size_t e = i * k + j;
+      const Pt ci = load_g1(commits + 3 * e, ok);
+      const uint32_t m = load_set(sets, e, ok);
+      uint32_t wi = weights[e];
+      if (wi >= HFP) {
+        ok = false;
+        wi = 0;
+      }
+      uint32_t r = 0;
+      for (uint32_t a = 0; a < SET_BITS; a++) {
+        if (!((m >> a) & 1u)) continue;
+        uint32_t ya = ys[SET_BITS * e + a];
+        if (ya >= HFP) {
+          ok = false;
+          ya = 0;
+        }
+        const uint32_t rest = m & ~(1u << a);
+        const uint32_t l = hf17::mod17(vanish_at(rest, u) * hf17::inv_canon(vanish_at(rest, a)));   // the Lagrange basis at u
+        r += hf17::mod17(ya * l);
+      }
+      fold_entry(G, c, y, ci, hf17::mod17(wi * vanish_at(T & ~m, u)), hf17::mod17(r));   // (r <= 16 x 16)
+    }
+    const Pt w = load_g1(proofs + 6 * i, ok);
+    const Pt wp = load_g1(proofs + 6 * i + 3, ok);
+    fold_entry(G, c, y, w, hf17::neg(vanish_at(T, u)), 0u);
+    okb[i] = (uint8_t)opening_check(G, vk, c, y, wp, u, ok);
   }
 }
 
@@ -249,10 +328,11 @@ int check_vk(const char* fn, const plk_kzg_vk_t* vk, VkWords* w) {
   *w = VkWords{vk->g1[0], vk->g1[1], vk->g1[2], vk->g2_1[0], vk->g2_1[1], vk->g2_s[0], vk->g2_s[1]};
   return PLK_OK;
 }
-// folded verification: k in 1 .. PLK_KZG_FOLD_MAX, then the pointers and n, the key, n k <= 2^30
-int check_fold_verify(const char* fn, const plk_kzg_vk_t* vk, int k, bool null_arg, size_t n, VkWords* w) {
-  if (k < 1 || k > PLK_KZG_FOLD_MAX) {
-    plk_set_error("%s: k = %d is outside 1 .. %d", fn, k, PLK_KZG_FOLD_MAX);
+// folded and multi-point verification: k in 1 .. kmax, then the pointers and n, the key, n k <= 2^30
+int check_fold_verify(const char* fn, const plk_kzg_vk_t* vk, int k, bool null_arg, size_t n, VkWords* w,
+                      int kmax = PLK_KZG_FOLD_MAX) {
+  if (k < 1 || k > kmax) {
+    plk_set_error("%s: k = %d is outside 1 .. %d", fn, k, kmax);
     return PLK_ERR_ARG;
   }
   int rc = check_n(fn, !vk || null_arg, n);
@@ -350,6 +430,49 @@ int plk_kzg_verify_fold_batch(const plk_kzg_vk_t* vk, int k, const uint8_t* comm
   PLK_HIP(hipMemcpy(d_w, proofs3, 3 * n, hipMemcpyHostToDevice));
   PLK_HIP(hipMemcpy(d_z, zs, n, hipMemcpyHostToDevice));
   if ((rc = plk_kzg_verify_fold_batch_dev(vk, k, d_c, d_wt, d_y, d_z, d_w, n, d_ok, nullptr))) return rc;
+  PLK_HIP(hipMemcpy(ok, d_ok, n, hipMemcpyDeviceToHost));
+  return PLK_OK;
+}
+
+int plk_kzg_verify_multi_batch_dev(const plk_kzg_vk_t* vk, int k, const uint8_t* d_commits3, const uint32_t* d_sets,
+                                   const uint8_t* d_weights, const uint8_t* d_ys, const uint8_t* d_us, const uint8_t* d_proofs6,
+                                   size_t n, uint8_t* d_ok, void* stream) {
+  const char* fn = "plk_kzg_verify_multi_batch_dev";
+  VkWords w;
+  int rc = check_fold_verify(fn, vk, k, !d_commits3 || !d_sets || !d_weights || !d_ys || !d_us || !d_proofs6 || !d_ok, n, &w,
+                             PLK_KZG_MULTI_MAX);
+  if (rc) return rc;
+  if ((uintptr_t)d_sets % 4) {
+    plk_set_error("%s: d_sets must be 4-byte aligned", fn);
+    return PLK_ERR_ARG;
+  }
+  if ((rc = plk_use_device())) return rc;
+  hipLaunchKernelGGL(kzg_verify_multi_kernel, dim3(blocks_for(n)), dim3(PAIR_T), 0, (hipStream_t)stream, w, (uint32_t)k,
+                     d_commits3, d_sets, d_weights, d_ys, d_us, d_proofs6, n, d_ok);
+  PLK_HIP(hipGetLastError());
+  return PLK_OK;
+}
+
+int plk_kzg_verify_multi_batch(const plk_kzg_vk_t* vk, int k, const uint8_t* commits3, const uint32_t* sets,
+                               const uint8_t* weights, const uint8_t* ys, const uint8_t* us, const uint8_t* proofs6, size_t n,
+                               uint8_t* ok) {
+  const char* fn = "plk_kzg_verify_multi_batch";
+  VkWords w;
+  int rc = check_fold_verify(fn, vk, k, !commits3 || !sets || !weights || !ys || !us || !proofs6 || !ok, n, &w, PLK_KZG_MULTI_MAX);
+  if (rc || (rc = plk_select_device())) return rc;
+  const size_t e = n * (size_t)k;   // entries
+  PlkScratch S;
+  if ((rc = S.alloc(fn, 25 * e + 8 * n))) return rc;
+  // (the masks first: the allocation is aligned)
+  uint8_t *d_s = S.d, *d_c = d_s + 4 * e, *d_wt = d_c + 3 * e, *d_y = d_wt + e, *d_w = d_y + 17 * e, *d_u = d_w + 6 * n,
+          *d_ok = d_u + n;
+  PLK_HIP(hipMemcpy(d_s, sets, 4 * e, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_c, commits3, 3 * e, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_wt, weights, e, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_y, ys, 17 * e, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_w, proofs6, 6 * n, hipMemcpyHostToDevice));
+  PLK_HIP(hipMemcpy(d_u, us, n, hipMemcpyHostToDevice));
+  if ((rc = plk_kzg_verify_multi_batch_dev(vk, k, d_c, (const uint32_t*)d_s, d_wt, d_y, d_u, d_w, n, d_ok, nullptr))) return rc;
   PLK_HIP(hipMemcpy(ok, d_ok, n, hipMemcpyDeviceToHost));
   return PLK_OK;
 }

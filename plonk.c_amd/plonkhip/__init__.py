@@ -114,6 +114,15 @@ SIGNATURES = {
                                               C.c_int, _vp, _vp, C.POINTER(_vp), _vp, _vp]),
     "plk_kzg_verify_fold_batch": (C.c_int, [_vp, C.c_int, _u8p, _u8p, _u8p, _u8p, _u8p, _sz, _u8p]),
     "plk_kzg_verify_fold_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "plk_kzg_multi_coeffs": (C.c_int, [C.POINTER(C.c_uint32), _u8p, C.c_int, C.c_uint8, _u8p]),
+    "plk_kzg_multi_workspace": (_sz, [C.POINTER(_sz), C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_int]),
+    "plk_kzg_open_multi_batch": (C.c_int, [_vp, C.POINTER(_u8p), C.POINTER(_sz), C.POINTER(C.c_uint32), _u8p,
+                                           C.POINTER(C.c_int), _u8p, C.c_int, _u8p, _u8p]),
+    "plk_kzg_open_multi_batch_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(C.c_uint32), _u8p,
+                                               C.POINTER(C.c_int), _u8p, C.c_int, _vp, _vp, C.POINTER(_vp), _vp, _vp]),
+    "plk_kzg_verify_multi_batch": (C.c_int, [_vp, C.c_int, _u8p, C.POINTER(C.c_uint32), _u8p, _u8p, _u8p, _u8p, _sz,
+                                             _u8p]),
+    "plk_kzg_verify_multi_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "plk_poly_lincomb_len": (_sz, [_vp]),
     "plk_poly_lincomb": (C.c_int, [_vp, C.POINTER(_sz)]),
     "plk_poly_lincomb_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -740,6 +749,101 @@ def kzg_verify_fold_dev(vk, k, commits, weights, ys, zs, proofs, n, ok, stream=N
     """vk: a KzgVk on the host; the rest device tensors (or raw pointers) of any alignment; ok: n bytes"""
     _check("plk_kzg_verify_fold_batch_dev", lib().plk_kzg_verify_fold_batch_dev(
         C.byref(vk), int(k), _ptr(commits), _ptr(weights), _ptr(ys), _ptr(zs), _ptr(proofs), int(n), _ptr(ok),
+        _stream(stream)))
+
+
+# ---------------------------------------------------------------- KZG multi-point openings
+PLK_KZG_MULTI_MAX = 15
+PLK_KZG_MULTI_POINTS = 16
+
+
+def _u32s(a):
+    v = [int(x) for x in a]
+    return (C.c_uint32 * max(len(v), 1))(*v)
+
+
+def kzg_multi_coeffs(sets, weights, u):
+    """plk_kzg_multi_coeffs: sets = one mask per polynomial (bit a set: the point a) -> the k + 1 weights of the
+    second proof's fold, c_i = w_i prod_{a in T \\ S_i} (u - a) and (17 - c_T) % 17.  No device needed."""
+    k = len(sets)
+    wa = _u8(weights).reshape(-1)
+    if wa.size != k:
+        raise ValueError("one weight per set")
+    out = np.zeros(k + 1, np.uint8)
+    _check("plk_kzg_multi_coeffs", lib().plk_kzg_multi_coeffs(_u32s(sets), _p(wa), k, int(u), _p(out)))
+    return [int(v) for v in out]
+
+
+def kzg_multi_workspace(lens, sets, start):
+    """plk_kzg_multi_workspace: bytes of d_work for kzg_open_multi_dev; start: the ngroups + 1 group
+    boundaries in the flat arrays.  No device needed; 0 for bad arguments."""
+    ng = len(start) - 1
+    ls = (_sz * max(len(lens), 1))(*[int(v) for v in lens])
+    st = (C.c_int * max(len(start), 1))(*[int(v) for v in start])
+    return int(lib().plk_kzg_multi_workspace(ls, _u32s(sets), st, ng))
+
+
+def kzg_open_multi(srs, groups, sets, weights, us):
+    """plk_kzg_open_multi_batch: groups = [[polynomial, ...], ...] (1 .. 15 each), sets (masks) and weights the
+    same shape, one u per group -> ([[17-byte row per polynomial, ...], ...], [6 proof bytes W, W' per group]);
+    row[a] = p_i(a) for a in S_i, 0xFF elsewhere"""
+    if any(len(x) != len(groups) for x in (sets, weights)) or \
+            any(len(w) != len(g) or len(m) != len(g) for w, m, g in zip(weights, sets, groups)):
+        raise ValueError("one set and one weight per polynomial")
+    arrs, ptrs, lens, n = _host_polys([p for g in groups for p in g])
+    wa = _u8([w for g in weights for w in g]).reshape(-1)
+    ua = _u8(us).reshape(-1)
+    ng = len(groups)
+    if ua.size != ng:
+        raise ValueError("one u per group")
+    start = _fold_start(len(g) for g in groups)
+    ys = np.zeros(17 * max(n, 1), np.uint8)
+    out = np.zeros(6 * max(ng, 1), np.uint8)
+    _check("plk_kzg_open_multi_batch", lib().plk_kzg_open_multi_batch(
+        _srs_h(srs), ptrs, lens, _u32s([m for g in sets for m in g]), _p(wa), start, _p(ua), ng, _p(ys), _p(out)))
+    return ([[bytes(ys[17 * i:17 * i + 17]) for i in range(start[g], start[g + 1])] for g in range(ng)],
+            [bytes(out[6 * g:6 * g + 6]) for g in range(ng)])
+
+
+def kzg_open_multi_dev(srs, polys, lens, sets, weights, start, us, ys, res, hs=None, work=None, stream=None):
+    """polys: the flat list of device tensors (or raw pointers), group g = [start[g], start[g + 1]); lens, sets,
+    weights, start, us: host values; ys: 17 len(polys) device bytes; res: two zeroed records per group (W at
+    2 g, W' at 2 g + 1); hs: None, or per group None / Lh device bytes; work: kzg_multi_workspace(lens, sets,
+    start) device bytes."""
+    n = len(polys)
+    ng = len(start) - 1
+    ptrs = (_vp * max(n, 1))(*[_ptr(p) for p in polys])
+    ls = (_sz * max(n, 1))(*[int(v) for v in lens])
+    st = (C.c_int * max(len(start), 1))(*[int(v) for v in start])
+    wa = _u8(weights).reshape(-1)
+    ua = _u8(us).reshape(-1)
+    hp = None if hs is None else (_vp * max(ng, 1))(*[_ptr(h) for h in hs])
+    _check("plk_kzg_open_multi_batch_dev", lib().plk_kzg_open_multi_batch_dev(
+        _srs_h(srs), ptrs, ls, _u32s(sets), _p(wa), st, _p(ua), ng, _ptr(ys), _ptr(res), hp, _ptr(work), _stream(stream)))
+
+
+def kzg_verify_multi(vk, k, commits, sets, weights, ys, us, proofs):
+    """plk_kzg_verify_multi_batch: job b owns entries [k b, k (b + 1)) of commits (3 bytes each), sets (masks),
+    weights and ys (17-byte rows); one u and six proof bytes W, W' per job -> n bytes, 1 accept / 0 reject /
+    2 an invalid byte in the job"""
+    c, w = _u8(commits).reshape(-1), _u8(proofs).reshape(-1)
+    wa, ya, ua = _u8(weights).reshape(-1), _u8(ys).reshape(-1), _u8(us).reshape(-1)
+    sa = np.ascontiguousarray(np.asarray(sets, dtype=np.uint32).reshape(-1))
+    n = ua.size
+    e = n * int(k)
+    if c.size != 3 * e or wa.size != e or sa.size != e or ya.size != 17 * e or w.size != 6 * n:
+        raise ValueError("n k commitments, sets, weights and 17-byte rows of ys; n us and 6-byte proofs")
+    ok = np.zeros(max(n, 1), np.uint8)
+    _check("plk_kzg_verify_multi_batch", lib().plk_kzg_verify_multi_batch(
+        C.byref(vk), int(k), _p(c), sa.ctypes.data_as(C.POINTER(C.c_uint32)), _p(wa), _p(ya), _p(ua), _p(w), n, _p(ok)))
+    return ok[:n]
+
+
+def kzg_verify_multi_dev(vk, k, commits, sets, weights, ys, us, proofs, n, ok, stream=None):
+    """vk: a KzgVk on the host; the rest device tensors (or raw pointers) of any alignment, the masks
+    (4 bytes each) 4-byte aligned; ok: n bytes"""
+    _check("plk_kzg_verify_multi_batch_dev", lib().plk_kzg_verify_multi_batch_dev(
+        C.byref(vk), int(k), _ptr(commits), _ptr(sets), _ptr(weights), _ptr(ys), _ptr(us), _ptr(proofs), int(n), _ptr(ok),
         _stream(stream)))
 
 
