@@ -10,9 +10,9 @@
 //   h = sum_{a in T} (G_a - G_a(a)) / (x - a),   G_a = sum_{i : a in S_i} (w_i lambda_ia mod 17) p_i,   T = union S_i
 //
 // -- at most 17 single-point quotients per group however many (polynomial, point) pairs there are.  Each is
-// what the opening kernel of kzg.hip forms: a suffix sum with weights a^(j mod 16) (a^16 = 1 for a != 0), the
-// carry into a 4096-coefficient chunk the plain sum of the later chunks' aggregates; a = 0 is the shift
-// q[j] = G_0[j + 1].  The launches of a call, four whole groups at a time:
+// what the opening kernel of kzg.hip forms, by the same device pieces (plk_kzg_open.h: suffix_carry and
+// quotient16 for a != 0, shift16 for a = 0, then store16 and the finish; host side plk_kzg_host.h).
+// The launches of a call, four whole groups at a time:
 //   multi_agg_kernel   only when some polynomial exceeds one chunk; block (chunk >= 1, group): one word per
 //                      (polynomial, point a != 0 of its set, chunk) = sum_j p[j] a^(j mod 16) mod 17 with the
 //                      >= 17 flag in bit 8 (the polynomial's bytes loaded once for all its points), and one
@@ -31,25 +31,23 @@
 #include <algorithm>
 #include <vector>
 
-#include "kzg_multi.h"
 #include "plk_device.h"
 #include "plk_hf17.h"
 #include "plk_hostcall.h"
-#include "plk_msm_finish.h"
+#include "plk_kzg_host.h"
+#include "plk_kzg_open.h"
 
 namespace {
 
-constexpr int MT = 256, ME = 16, MCHUNK = MT * ME;   // the chunk of kzg.hip: the fold launcher reads h by it
-constexpr int MWAVES = MT / PLK_WAVE;
 constexpr uint32_t HFP = hf17::P;
 constexpr int NPTS = 17;                              // GF(17) points
 constexpr int MULTI_GROUPS = 4;                       // whole groups per launch
 constexpr int MULTI_POLYS = MULTI_GROUPS * PLK_KZG_MULTI_MAX;
 constexpr uint32_t FULL_MASK = (1u << NPTS) - 1;
 using hf17::any_noncanonical;
-using hf17::byte_of;
 using hf17::mod17;
-using hf17::wave_suffix;
+using kzgo::dot16;
+using kzgo::packed_powers;
 
 struct MultiPoly {
   const uint8_t* p;
@@ -73,33 +71,12 @@ struct MultiBatch {
 };
 static_assert(sizeof(MultiBatch) <= 3072, "the batch travels as a kernel argument");
 
-// a^0 .. a^15 mod 17, four to a word (uniform)
-__device__ __forceinline__ void packed_powers(uint32_t a, uint32_t (&pk)[4]) {
-  uint32_t v = 1;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    uint32_t w = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      w |= v << (8 * j);
-      v = v * a % HFP;
-    }
-    pk[i] = w;
-  }
-}
-// sum_j byte j of w x a^j (<= 16 x 255 x 16): v_dot4_u32_u8 on genuine bytes
-__device__ __forceinline__ uint32_t dot16(const uint32_t (&w)[4], const uint32_t (&pk)[4]) {
-  uint32_t t = __builtin_amdgcn_udot4(w[0], pk[0], 0u, false);
-  t = __builtin_amdgcn_udot4(w[1], pk[1], t, false);
-  t = __builtin_amdgcn_udot4(w[2], pk[2], t, false);
-  return __builtin_amdgcn_udot4(w[3], pk[3], t, false);
-}
-
 // Coefficients [base, base + 16) of polynomials i0 .. i0 + NB - 1 of group G, zero past a polynomial's end
 // and in the slots past k.  Decided per polynomial, so a ragged group keeps its long polynomials on the fast
 // path: first every polynomial that is aligned and holds the whole run takes one vector load (predicated, all
 // in flight together), then the few runs left -- a polynomial's last partial run, an unaligned polynomial --
-// go byte by byte, each byte shifted in from the top (no indexed registers).
+// go byte by byte (kzgo::load16_rolled).  kzg.hip's fold_load decides once for the whole group instead; the
+// two policies issue different loads for a ragged group, so each file keeps its own.
 template <int NB>
 __device__ __forceinline__ void multi_load(const MultiBatch& B, const MultiGroup& G, uint32_t i0, uint64_t base,
                                            uint32_t (&w)[NB][4]) {
@@ -108,28 +85,14 @@ __device__ __forceinline__ void multi_load(const MultiBatch& B, const MultiGroup
     w[u][0] = w[u][1] = w[u][2] = w[u][3] = 0;
     if (i0 + u < G.k) {   // (uniform)
       const MultiPoly& P = B.p[G.first + i0 + u];
-      if (((uintptr_t)P.p & 15u) == 0 && base + 16 <= P.len) {
-        const uint4 v = *reinterpret_cast<const uint4*>(P.p + base);
-        w[u][0] = v.x; w[u][1] = v.y; w[u][2] = v.z; w[u][3] = v.w;
-      }
+      if (kzgo::aligned16(P.p) && base + 16 <= P.len) kzgo::load16_vec(P.p, base, w[u]);
     }
   }
 #pragma unroll
   for (int u = 0; u < NB; u++) {
     if (i0 + u < G.k) {   // (uniform)
       const MultiPoly& P = B.p[G.first + i0 + u];
-      if (!(((uintptr_t)P.p & 15u) == 0 && base + 16 <= P.len) && base < P.len) {
-        uint32_t x0 = 0, x1 = 0, x2 = 0, x3 = 0;
-#pragma nounroll
-        for (int j = 0; j < 16; j++) {
-          const uint32_t b = base + j < P.len ? P.p[base + j] : 0u;
-          x0 = x0 >> 8 | x1 << 24;
-          x1 = x1 >> 8 | x2 << 24;
-          x2 = x2 >> 8 | x3 << 24;
-          x3 = x3 >> 8 | b << 24;
-        }
-        w[u][0] = x0; w[u][1] = x1; w[u][2] = x2; w[u][3] = x3;
-      }
+      if (!(kzgo::aligned16(P.p) && base + 16 <= P.len) && base < P.len) kzgo::load16_rolled(P.p, P.len, base, w[u]);
     }
   }
 }
@@ -140,15 +103,15 @@ __device__ __forceinline__ uint32_t point_weight(const MultiGroup& G, uint32_t a
 
 // Aggregates of chunk blockIdx.x + 1 of group blockIdx.y (see the head of this file).
 constexpr int AGG_NB = 4;
-__global__ __launch_bounds__(MT) void multi_agg_kernel(MultiBatch B, uint32_t* __restrict__ work) {
-  __shared__ uint32_t psum[PLK_KZG_MULTI_MAX][NPTS - 1][MWAVES];   // per wave: the sum mod 17
-  __shared__ uint32_t pbad[PLK_KZG_MULTI_MAX][MWAVES];
+__global__ __launch_bounds__(kzgo::T) void multi_agg_kernel(MultiBatch B, uint32_t* __restrict__ work) {
+  __shared__ uint32_t psum[PLK_KZG_MULTI_MAX][NPTS - 1][kzgo::WAVES];   // per wave: the sum mod 17
+  __shared__ uint32_t pbad[PLK_KZG_MULTI_MAX][kzgo::WAVES];
   __shared__ uint32_t pfin[PLK_KZG_MULTI_MAX][NPTS - 1];
   const MultiGroup& G = B.g[blockIdx.y];
   const uint32_t c = blockIdx.x + 1;
   if (c >= G.nchunk) return;
   const uint32_t lane = threadIdx.x & (PLK_WAVE - 1), wv = threadIdx.x / PLK_WAVE;
-  const uint64_t base = (uint64_t)c * MCHUNK + (uint64_t)threadIdx.x * ME;
+  const uint64_t base = (uint64_t)c * kzgo::CHUNK + (uint64_t)threadIdx.x * kzgo::E;
   for (uint32_t i0 = 0; i0 < G.k; i0 += AGG_NB) {   // (uniform)
     uint32_t w[AGG_NB][4];
     multi_load<AGG_NB>(B, G, i0, base, w);
@@ -171,7 +134,7 @@ __global__ __launch_bounds__(MT) void multi_agg_kernel(MultiBatch B, uint32_t* _
   __syncthreads();
   {
     const uint32_t i = threadIdx.x / (NPTS - 1), a = threadIdx.x % (NPTS - 1) + 1;
-    if (i < G.k) {   // (MT >= 15 x 16)
+    if (i < G.k) {   // (kzgo::T >= 15 x 16)
       const MultiPoly& P = B.p[G.first + i];
       uint32_t s = 0;
       if ((P.mask >> a) & 1u) {
@@ -200,24 +163,22 @@ __global__ __launch_bounds__(MT) void multi_agg_kernel(MultiBatch B, uint32_t* _
 // that holds the launch's largest group.  srs_bad: the SRS has no log form (every record is then flagged; ys
 // and h are still exact).  res: the launch's first W record (group y at res + 2 y).
 template <int NB>
-__global__ __launch_bounds__(MT) void multi_open_kernel(MultiBatch B, const uint8_t* __restrict__ logs,
+__global__ __launch_bounds__(kzgo::T) void multi_open_kernel(MultiBatch B, const uint8_t* __restrict__ logs,
                                                        const uint32_t* __restrict__ work, uint8_t* __restrict__ ys,
                                                        PlkMsmResult* res, const uint32_t* __restrict__ exp_words,
                                                        uint32_t srs_bad, uint32_t row0) {
-  __shared__ uint32_t etab[PLK_GROUP_ORDER];
-  __shared__ uint32_t wsum[MWAVES];
-  __shared__ uint32_t wbad[MWAVES];
-  __shared__ uint32_t ws[2][2 * MWAVES];   // per point, alternating: the waves' totals, the waves' carry shares
-  __shared__ uint32_t ysum[PLK_KZG_MULTI_MAX][NPTS][MWAVES];
+  __shared__ kzgo::Finish fin;
+  __shared__ uint32_t ws[2][2 * kzgo::WAVES];   // suffix_carry's words, alternating from point to point
+  __shared__ uint32_t ysum[PLK_KZG_MULTI_MAX][NPTS][kzgo::WAVES];
   const MultiGroup& G = B.g[blockIdx.y];
   const uint32_t c = blockIdx.x;
   if (c >= G.nchunk) return;
-  if (threadIdx.x < PLK_GROUP_ORDER) etab[threadIdx.x] = exp_words[threadIdx.x];
-  const uint64_t base = (uint64_t)c * MCHUNK + (uint64_t)threadIdx.x * ME;
+  fin.stage(exp_words);
+  const uint64_t base = (uint64_t)c * kzgo::CHUNK + (uint64_t)threadIdx.x * kzgo::E;
   const uint32_t wv = threadIdx.x / PLK_WAVE, lane = threadIdx.x & (PLK_WAVE - 1);
   bool bad = srs_bad != 0;
   // tr[q][j]: byte j of polynomials 4q .. 4q + 3, polynomial 4q + u in byte u
-  uint32_t tr[NB / 4][ME];
+  uint32_t tr[NB / 4][kzgo::E];
   {
     uint32_t w[NB][4];
     multi_load<NB>(B, G, 0, base, w);
@@ -233,7 +194,7 @@ __global__ __launch_bounds__(MT) void multi_open_kernel(MultiBatch B, const uint
           if (u < (int)G.k && ((B.p[G.first + u].mask >> a) & 1u)) {   // (uniform)
             const MultiPoly& P = B.p[G.first + u];
             uint32_t v = dot16(w[u], pk);   // (<= 16 x 255 x 16)
-            for (uint32_t b = 1 + threadIdx.x; b < G.nchunk; b += MT) v += work[P.work + (a - 1) * G.nchunk + b] & 0xFFu;
+            for (uint32_t b = 1 + threadIdx.x; b < G.nchunk; b += kzgo::T) v += work[P.work + (a - 1) * G.nchunk + b] & 0xFFu;
             const uint32_t s = plk_wave_sum(v);
             if (lane == 0) ysum[u][a][wv] = s;
           }
@@ -246,19 +207,19 @@ __global__ __launch_bounds__(MT) void multi_open_kernel(MultiBatch B, const uint
       for (int m = 0; m < 4; m++)
 #pragma unroll
         for (int j = 0; j < 4; j++)
-          tr[q][4 * m + j] = ((w[4 * q][m] >> (8 * j)) & 0xFFu) | ((w[4 * q + 1][m] >> (8 * j)) & 0xFFu) << 8 |
-                             ((w[4 * q + 2][m] >> (8 * j)) & 0xFFu) << 16 | ((w[4 * q + 3][m] >> (8 * j)) & 0xFFu) << 24;
+          tr[q][4 * m + j] = kzgo::transpose4(w[4 * q][m], w[4 * q + 1][m], w[4 * q + 2][m], w[4 * q + 3][m], j);
   }
-  uint32_t hacc[ME];   // sum over the points of T of the quotient bytes (<= 17 x 16)
+  uint32_t hacc[kzgo::E];   // sum over the points of T of the quotient bytes (<= 17 x 16)
 #pragma unroll
-  for (int j = 0; j < ME; j++) hacc[j] = 0;
+  for (int j = 0; j < kzgo::E; j++) hacc[j] = 0;
+  const auto add = [&hacc](int j, uint32_t q) { hacc[j] += q; };
   uint32_t par = 0;
   for (uint32_t m = G.tmask; m; m &= m - 1) {   // (uniform) the points of T
     const uint32_t a = (uint32_t)__builtin_ctz(m);
     // G_a's sixteen canonical bytes: sum_i weight x byte <= 15 x 16 x 255 = 61200, inside mod17's range
     uint32_t nb[4] = {0, 0, 0, 0};
 #pragma unroll
-    for (int j = 0; j < ME; j++) {
+    for (int j = 0; j < kzgo::E; j++) {
       uint32_t t = 0;
 #pragma unroll
       for (int q = 0; q < NB / 4; q++) t = __builtin_amdgcn_udot4(tr[q][j], G.wpk[a][q], t, false);
@@ -268,32 +229,9 @@ __global__ __launch_bounds__(MT) void multi_open_kernel(MultiBatch B, const uint
       uint32_t pk[4];
       packed_powers(a, pk);
       const uint32_t tot = mod17(dot16(nb, pk));   // (<= 16 x 16 x 16)
-      uint32_t cs = 0;
-      for (uint32_t b = c + 1 + threadIdx.x; b < G.nchunk; b += MT) {
-        const uint32_t v = work[G.work + (a - 1) * G.nchunk + b];
-        cs += v & 0xFFu;
-        bad |= (v >> 8) != 0;
-      }
-      const uint32_t suf = wave_suffix(tot);   // this lane's coefficients and every later lane's
-      const uint32_t cw = plk_wave_sum(cs % HFP);
-      if (lane == 0) {
-        ws[par][wv] = suf;   // lane 0: the wave's total
-        ws[par][MWAVES + wv] = cw;
-      }
-      __syncthreads();
-      uint32_t run = suf - tot;   // the aggregates of the threads after this one, and the carry
-#pragma unroll
-      for (int u = 0; u < MWAVES; u++) run += (u > (int)wv ? ws[par][u] : 0u) + ws[par][MWAVES + u];
+      const uint32_t run = kzgo::suffix_carry(tot, work + G.work + (a - 1) * G.nchunk, c, G.nchunk, ws[par], bad);
       par ^= 1u;   // (the next point's words: a wave may arrive there while another still reads these)
-      // run = sum_{i >= base + 16} G_a[i] a^i and a^-(base + 16) = 1: the thread's top quotient byte is run
-      // itself, the others follow the division's recurrence q[j] = G_a[j + 1] + a q[j + 1]
-      uint32_t qv = run % HFP;
-      hacc[ME - 1] += qv;
-#pragma unroll
-      for (int j = ME - 2; j >= 0; j--) {
-        qv = mod17(byte_of(nb, j + 1) + a * qv);   // (<= 16 + 16 x 16)
-        hacc[j] += qv;
-      }
+      kzgo::quotient16(nb, a, run, add);
     } else {
       // a = 0: q[j] = G_0[j + 1]; the thread's last quotient byte is G_0[base + 16], folded from the
       // polynomials' bytes (the next thread's, or the next chunk's, first coefficient)
@@ -303,20 +241,18 @@ __global__ __launch_bounds__(MT) void multi_open_kernel(MultiBatch B, const uint
         const uint32_t wt = point_weight(G, 0, i);
         if (wt != 0 && base + 16 < P.len) sn += wt * P.p[base + 16];
       }
-#pragma unroll
-      for (int j = 0; j < ME - 1; j++) hacc[j] += byte_of(nb, j + 1);
-      hacc[ME - 1] += mod17(sn);   // (<= 61200)
+      kzgo::shift16(nb, mod17(sn), add);   // (<= 61200)
     }
   }
   // h's sixteen canonical bytes, nothing past Lh (there the sums cancel mod 17 for canonical input)
   const uint64_t lh = G.lh;
   uint32_t o[4] = {0, 0, 0, 0};
 #pragma unroll
-  for (int j = 0; j < ME; j++) o[j >> 2] |= (base + j < lh ? mod17(hacc[j]) : 0u) << (8 * (j & 3));   // (hacc <= 272)
+  for (int j = 0; j < kzgo::E; j++) o[j >> 2] |= (base + j < lh ? mod17(hacc[j]) : 0u) << (8 * (j & 3));   // (hacc <= 272)
   if (c == 0) {
     __syncthreads();   // (uniform) ysum is complete
     const uint32_t i = threadIdx.x / NPTS, a = threadIdx.x % NPTS;
-    if (i < G.k) {   // (MT >= 15 x 17)
+    if (i < G.k) {   // (kzgo::T >= 15 x 17)
       const MultiPoly& P = B.p[G.first + i];
       uint32_t y = 0xFFu;
       if ((P.mask >> a) & 1u)
@@ -325,26 +261,10 @@ __global__ __launch_bounds__(MT) void multi_open_kernel(MultiBatch B, const uint
       ys[(size_t)NPTS * (G.first + i) + a] = (uint8_t)y;
     }
   }
-  if (base < lh) {
-    if (((uintptr_t)G.h & 15u) == 0 && base + 16 <= lh) {
-      *reinterpret_cast<uint4*>(G.h + base) = make_uint4(o[0], o[1], o[2], o[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 16; j++)
-        if (base + j < lh) G.h[base + j] = (uint8_t)(o[j >> 2] >> (8 * (j & 3)));
-    }
-  }
-  uint4 lg = make_uint4(0, 0, 0, 0);
-  if (!srs_bad && base < lh) lg = *reinterpret_cast<const uint4*>(logs + base);   // (logs: zero padded to 16)
-  uint32_t t = __builtin_amdgcn_udot4(lg.x, o[0], 0u, false);   // 16 x 101 x 16
-  t = __builtin_amdgcn_udot4(lg.y, o[1], t, false);
-  t = __builtin_amdgcn_udot4(lg.z, o[2], t, false);
-  t = __builtin_amdgcn_udot4(lg.w, o[3], t, false);
-  (void)msm_finish_xy<MT>(t % PLK_GROUP_ORDER, bad, res + 2 * blockIdx.y, wsum, wbad, etab, c, G.nchunk,
-                          row0 + blockIdx.y);
+  if (base < lh) kzgo::store16(G.h, lh, base, kzgo::aligned16(G.h), o);
+  fin.finish(kzgo::Finish::logs(logs, srs_bad, base, lh), o, bad, res + 2 * blockIdx.y, c, G.nchunk, row0 + blockIdx.y);
 }
 
-uint64_t chunks_of(uint64_t len) { return (len + MCHUNK - 1) / MCHUNK; }
 bool mask_ok(uint32_t m) { return m != 0 && (m & ~FULL_MASK) == 0 && m != FULL_MASK; }
 uint32_t inv17(uint32_t a) {
   uint32_t r = 1;
@@ -357,16 +277,6 @@ uint32_t vanish_at(uint32_t m, uint32_t u) {
   for (uint32_t a = 0; a < NPTS; a++)
     if ((m >> a) & 1u) r = r * ((u + HFP - a) % HFP) % HFP;
   return r;
-}
-
-// the group layout of a call: start[0] = 0, strictly increasing, at most PLK_KZG_MULTI_MAX a group
-bool layout_ok(const int* start, int ngroups) {
-  if (!start || ngroups <= 0 || start[0] != 0) return false;
-  for (int g = 0; g < ngroups; g++) {
-    const long long k = (long long)start[g + 1] - start[g];
-    if (k < 1 || k > PLK_KZG_MULTI_MAX) return false;
-  }
-  return true;
 }
 
 // the lengths of group g: the longest polynomial and Lh = max_i max(len_i - t_i, 1)
@@ -394,7 +304,7 @@ struct GroupWork {
 GroupWork group_work(const size_t* lens, const uint32_t* sets, const int* start, int g) {
   const GroupLens L = group_lens(lens, sets, start, g);
   const int k = start[g + 1] - start[g];
-  const uint64_t nchunk = chunks_of(L.maxlen);
+  const uint64_t nchunk = plk_kzg_chunks_of(L.maxlen);
   size_t fl[PLK_KZG_FOLD_MAX];
   for (int i = 0; i < k; i++) fl[i] = lens[start[g] + i];
   fl[k] = (size_t)L.lh;
@@ -414,7 +324,7 @@ int check_multi(const char* fn, const plk_srs* s, const void* polys, const size_
     plk_set_error("%s: handle, arrays, outputs and ngroups > 0 are required", fn);
     return PLK_ERR_ARG;
   }
-  if (!layout_ok(start, ngroups)) {
+  if (!plk_kzg_layout_ok(start, ngroups, PLK_KZG_MULTI_MAX)) {
     plk_set_error("%s: start must rise strictly from 0 by at most %d polynomials a group", fn, PLK_KZG_MULTI_MAX);
     return PLK_ERR_ARG;
   }
@@ -439,28 +349,15 @@ int check_multi(const char* fn, const plk_srs* s, const void* polys, const size_
       }
     }
   }
-  for (int i = 0; i < start[ngroups]; i++) {
-    if (lens[i] > PLK_KZG_RECORD_MAX_LEN) {
-      plk_set_error("%s: polynomial %d: %zu coefficients exceed the %llu one record's finish can count", fn, i, lens[i],
-                    (unsigned long long)PLK_KZG_RECORD_MAX_LEN);
-      return PLK_ERR_RANGE;
-    }
-  }
+  int rc;
+  for (int i = 0; i < start[ngroups]; i++)
+    if ((rc = plk_kzg_check_record_len(fn, "polynomial", i, lens[i]))) return rc;
   for (int g = 0; g < ngroups; g++) {
     const GroupLens L = group_lens(lens, sets, start, g);
     const uint64_t need = std::max<uint64_t>(L.lh, std::max<uint64_t>(L.maxlen - 1, 1));   // (Lh <= the longest length)
-    if (need > s->len) {
-      plk_set_error("Poynomial degree exceeds SRS size: POLY degree: %zu, SRS supports up to degree: %zu", (size_t)need,
-                    s->len);
-      return PLK_ERR_RANGE;
-    }
+    if ((rc = plk_kzg_check_srs_len(s, (size_t)need))) return rc;
   }
-  if (plk_cur_device() != s->dev) {
-    plk_set_error("%s: the SRS lives on device %d but the calling thread's current device is %d", fn, s->dev,
-                  plk_cur_device());
-    return PLK_ERR_ARG;
-  }
-  return PLK_OK;
+  return plk_kzg_check_device(fn, s);
 }
 
 // c[0 .. k) = w_i prod_{a in T \ S_i} (u - a), c[k] = -prod_{a in T} (u - a) (arguments checked by the caller)
@@ -508,7 +405,7 @@ int launch_multi(const plk_srs* s, const uint8_t* const* d_polys, const size_t* 
       G.lh = L.lh;
       G.first = np;
       G.k = (uint32_t)k;
-      G.nchunk = (uint32_t)chunks_of(L.maxlen);
+      G.nchunk = (uint32_t)plk_kzg_chunks_of(L.maxlen);
       const uint32_t agg0 = (uint32_t)((off[g] + W.o_agg) / 4), per = (NPTS - 1) * G.nchunk;
       G.work = agg0 + (uint32_t)k * per;
       for (int i = 0; i < k; i++, np++) {
@@ -530,9 +427,9 @@ int launch_multi(const plk_srs* s, const uint8_t* const* d_polys, const size_t* 
       maxc = std::max(maxc, G.nchunk);
       maxk = std::max(maxk, G.k);
     }
-    if (maxc > 1) hipLaunchKernelGGL(multi_agg_kernel, dim3(maxc - 1, ng), dim3(MT), 0, st, B, words);
+    if (maxc > 1) hipLaunchKernelGGL(multi_agg_kernel, dim3(maxc - 1, ng), dim3(kzgo::T), 0, st, B, words);
     const auto open = maxk <= 4 ? multi_open_kernel<4> : maxk <= 8 ? multi_open_kernel<8> : maxk <= 12 ? multi_open_kernel<12> : multi_open_kernel<16>;
-    hipLaunchKernelGGL(open, dim3(maxc, ng), dim3(MT), 0, st, B, s->d_log, words, d_ys + (size_t)NPTS * start[g0],
+    hipLaunchKernelGGL(open, dim3(maxc, ng), dim3(kzgo::T), 0, st, B, s->d_log, words, d_ys + (size_t)NPTS * start[g0],
                        d_res + 2 * (size_t)g0, s->exp_words, bad, 2u * (uint32_t)g0);
     PLK_HIP(hipGetLastError());
   }
@@ -612,13 +509,11 @@ int compose_group(const plk_srs* s, const uint8_t* const* polys, const size_t* l
 int host_multi(const plk_srs* s, const uint8_t* const* polys, const size_t* lens, const uint32_t* sets,
                const uint8_t* weights, const int* start, const uint8_t* us, int ngroups, uint8_t* ys, uint8_t* proofs6) {
   const int np = start[ngroups];
-  size_t poly_bytes = 0;
-  for (int i = 0; i < np; i++) {
-    if (!polys[i]) {
-      plk_set_error("plk_kzg_open_multi_batch: polynomial %d is NULL", i);
-      return PLK_ERR_ARG;
-    }
-    poly_bytes += plk_pad16(lens[i]);
+  size_t poly_bytes;
+  const int null_at = plk_kzg_arena_bytes(polys, lens, np, &poly_bytes);
+  if (null_at >= 0) {
+    plk_set_error("plk_kzg_open_multi_batch: polynomial %d is NULL", null_at);
+    return PLK_ERR_ARG;
   }
   std::vector<uint32_t> irr(2 * (size_t)ngroups, 1u);
   if (!s->irregular) {
@@ -629,25 +524,13 @@ int host_multi(const plk_srs* s, const uint8_t* const* polys, const size_t* lens
     if (rc) return rc;
     PlkMsmResult* d_res = (PlkMsmResult*)(S.d + o_res);
     PLK_HIP(hipMemsetAsync(d_res, 0, 2 * (size_t)ngroups * sizeof(PlkMsmResult), s->st));
-    std::vector<const uint8_t*> dp(np);
-    size_t off = 0;
-    for (int i = 0; i < np; i++) {
-      dp[i] = S.d + off;
-      PLK_HIP(hipMemcpyAsync(S.d + off, polys[i], lens[i], hipMemcpyHostToDevice, s->st));
-      off += plk_pad16(lens[i]);
-    }
-    if ((rc = launch_multi(s, dp.data(), lens, sets, weights, start, us, ngroups, S.d + o_ys, d_res, nullptr, S.d + o_work,
+    std::vector<const uint8_t*> dp;
+    if ((rc = plk_kzg_upload(S, polys, lens, np, s->st, dp)) ||
+        (rc = launch_multi(s, dp.data(), lens, sets, weights, start, us, ngroups, S.d + o_ys, d_res, nullptr, S.d + o_work,
                            s->st)))
       return rc;
-    std::vector<uint8_t> h(32 * 2 * (size_t)ngroups);
-    PLK_HIP(hipMemcpy2DAsync(h.data(), 32, d_res, sizeof(PlkMsmResult), 32, 2 * (size_t)ngroups, hipMemcpyDeviceToHost, s->st));
     PLK_HIP(hipMemcpyAsync(ys, S.d + o_ys, (size_t)NPTS * np, hipMemcpyDeviceToHost, s->st));
-    PLK_HIP(hipStreamSynchronize(s->st));
-    for (int r = 0; r < 2 * ngroups; r++) {
-      const PlkMsmResult* rec = (const PlkMsmResult*)(h.data() + 32 * (size_t)r);
-      irr[r] = rec->irregular;
-      memcpy(proofs6 + 3 * r, rec->g1, 3);
-    }
+    if ((rc = plk_kzg_read_records(d_res, 2 * (size_t)ngroups, s->st, irr.data(), proofs6))) return rc;
   }
   for (int g = 0; g < ngroups; g++) {
     if (!irr[2 * g] && !irr[2 * g + 1]) continue;
@@ -680,7 +563,7 @@ int plk_kzg_multi_coeffs(const uint32_t* sets, const uint8_t* weights, int k, ui
 }
 
 size_t plk_kzg_multi_workspace(const size_t* lens, const uint32_t* sets, const int* start, int ngroups) {
-  if (!lens || !sets || !layout_ok(start, ngroups)) return 0;
+  if (!lens || !sets || !plk_kzg_layout_ok(start, ngroups, PLK_KZG_MULTI_MAX)) return 0;
   for (int i = 0; i < start[ngroups]; i++)
     if (lens[i] == 0 || lens[i] > PLK_KZG_RECORD_MAX_LEN || !mask_ok(sets[i])) return 0;
   size_t total = 0;

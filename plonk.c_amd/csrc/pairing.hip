@@ -12,7 +12,8 @@
 //            The formulas are applied blindly, as the reference applies them: no curve test, no subgroup
 //            test, and line() reads x and y whatever the flag says.
 //   verify   L = C - y G + z W built with the raw g1_mul / g1_neg / g1_add in the order the header
-//            fixes, then pairing(L, [1]_2) == pairing(W, [s]_2), all in registers, one byte out.
+//            fixes, then pairing(L, [1]_2) == pairing(W, [s]_2), all in registers, one byte out
+//            (opening_check: the one copy all three verification kernels call).
 //   fold     the same check on C = the raw fold of g1_mul(C_i, w_i) over a job's k commitments and
 //            y = sum_i w_i y_i: k uniform over the launch, so every lane runs the same k steps.
 //   multi    the folded check on (C_0 .. C_{k-1}, W) with proof W' (plonkhip.h, "KZG multi-point openings"):
@@ -158,6 +159,23 @@ __global__ __launch_bounds__(PAIR_T) void pairing_kernel(const uint8_t* __restri
   }
 }
 
+// The opening check on (C, y, W, z), y and z < 17: L = C - y G + z W, then pairing(L, [1]_2) == pairing(W, [s]_2).
+// 1 or 0; 2 when the job held an invalid byte (ok false).
+__device__ __forceinline__ uint32_t opening_check(const G1Ops& G, const VkWords& vk, Pt c, uint32_t y, Pt w, uint32_t z,
+                                                  bool ok) {
+  const Pt g{vk.gx, vk.gy, vk.ginf};
+  Pt l = G.add(c, G.negp(G.mul(g, y)));
+  l = G.add(l, G.mul(w, z));
+  const Gt lhs = pairing(G, l, vk.h1x, vk.h1y);
+  const Gt rhs = pairing(G, w, vk.hsx, vk.hsy);
+  return !ok ? 2u : (lhs.a == rhs.a && lhs.b == rhs.b) ? 1u : 0u;
+}
+// One entry of a folded check: C += g1_mul(C_i, w_i), y = hf_add(y, hf_mul(w_i, y_i)) (w_i, y_i < 17).
+__device__ __forceinline__ void fold_entry(const G1Ops& G, Pt& c, uint32_t& y, Pt ci, uint32_t wi, uint32_t yi) {
+  c = G.add(c, G.mul(ci, wi));
+  y = (y + wi * yi % HFP) % HFP;
+}
+
 __global__ __launch_bounds__(PAIR_T) void kzg_verify_kernel(VkWords vk, const uint8_t* __restrict__ commits,
                                                            const uint8_t* __restrict__ zs, const uint8_t* __restrict__ ys,
                                                            const uint8_t* __restrict__ proofs, size_t n,
@@ -165,7 +183,6 @@ __global__ __launch_bounds__(PAIR_T) void kzg_verify_kernel(VkWords vk, const ui
   __shared__ uint32_t invl[GFP];
   stage_inverses(invl);
   const G1Ops G{invl};
-  const Pt g{vk.gx, vk.gy, vk.ginf};
   for (size_t i = (size_t)blockIdx.x * PAIR_T + threadIdx.x; i < n; i += (size_t)gridDim.x * PAIR_T) {
     bool ok = true;
     const Pt c = load_g1(commits + 3 * i, ok);
@@ -175,28 +192,8 @@ __global__ __launch_bounds__(PAIR_T) void kzg_verify_kernel(VkWords vk, const ui
       ok = false;
       z = y = 0;
     }
-    Pt l = G.add(c, G.negp(G.mul(g, y)));
-    l = G.add(l, G.mul(w, z));
-    const Gt lhs = pairing(G, l, vk.h1x, vk.h1y);
-    const Gt rhs = pairing(G, w, vk.hsx, vk.hsy);
-    okb[i] = (uint8_t)(!ok ? 2u : (lhs.a == rhs.a && lhs.b == rhs.b) ? 1u : 0u);
+    okb[i] = (uint8_t)opening_check(G, vk, c, y, w, z, ok);
   }
-}
-
-// The two steps the folded checks share.  One entry: C += g1_mul(C_i, w_i), y = hf_add(y, hf_mul(w_i, y_i))
-// (w_i, y_i < 17).  The check of kzg_verify_kernel on (C, y, W, z): 2 when the job held an invalid byte.
-__device__ __forceinline__ void fold_entry(const G1Ops& G, Pt& c, uint32_t& y, Pt ci, uint32_t wi, uint32_t yi) {
-  c = G.add(c, G.mul(ci, wi));
-  y = (y + wi * yi % HFP) % HFP;
-}
-__device__ __forceinline__ uint32_t opening_check(const G1Ops& G, const VkWords& vk, Pt c, uint32_t y, Pt w, uint32_t z,
-                                                  bool ok) {
-  const Pt g{vk.gx, vk.gy, vk.ginf};
-  Pt l = G.add(c, G.negp(G.mul(g, y)));
-  l = G.add(l, G.mul(w, z));
-  const Gt lhs = pairing(G, l, vk.h1x, vk.h1y);
-  const Gt rhs = pairing(G, w, vk.hsx, vk.hsy);
-  return !ok ? 2u : (lhs.a == rhs.a && lhs.b == rhs.b) ? 1u : 0u;
 }
 
 // Folded verification, job i: C = the fold of its k commitments under its k weights and y = the fold
@@ -344,6 +341,34 @@ int check_fold_verify(const char* fn, const plk_kzg_vk_t* vk, int k, bool null_a
   return PLK_OK;
 }
 
+// The device arrays of one host form, one after another in the call's one allocation (alloc: the sum of
+// their sizes; the masks go first, so their 4-byte alignment costs no padding).  add() appends an array at
+// the next multiple of align, uploads it when it has a source and returns its device pointer; rc keeps the
+// first failure -- a copy, or an array that would pass the allocation -- and is read once after the last add().
+struct Staged {
+  PlkScratch S;
+  size_t cap = 0, off = 0;
+  int rc = PLK_OK;
+  int alloc(const char* fn, size_t bytes) {
+    cap = bytes;
+    return S.alloc(fn, bytes);
+  }
+  uint8_t* add(const void* src, size_t bytes, size_t align = 1) {
+    off = (off + align - 1) / align * align;
+    uint8_t* d = S.d + off;
+    off += bytes;
+    if (rc == PLK_OK && off > cap) {
+      plk_set_error("%s:%d the staged arrays pass the %zu bytes allocated for them", __FILE__, __LINE__, cap);
+      rc = PLK_ERR_ARG;
+    }
+    if (rc == PLK_OK && src && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      plk_set_error("%s:%d the upload of a staged array failed", __FILE__, __LINE__);
+      rc = PLK_ERR_HIP;
+    }
+    return d;
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -373,13 +398,11 @@ int plk_pairing_batch(const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t*
   const char* fn = "plk_pairing_batch";
   int rc = check_n(fn, !g1s || !g2s || !out_gt, n);
   if (rc || (rc = check_range(fn, n)) || (rc = plk_select_device())) return rc;
-  PlkScratch S;
-  if ((rc = S.alloc(fn, 7 * n))) return rc;
-  uint8_t *d_g1 = S.d, *d_g2 = S.d + 3 * n, *d_out = S.d + 5 * n;
-  PLK_HIP(hipMemcpy(d_g1, g1s, 3 * n, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_g2, g2s, 2 * n, hipMemcpyHostToDevice));
-  if ((rc = plk_pairing_batch_dev(d_g1, d_g2, n, d_out, nullptr))) return rc;
-  PLK_HIP(hipMemcpy(out_gt, d_out, 2 * n, hipMemcpyDeviceToHost));
+  Staged D;
+  if ((rc = D.alloc(fn, 3 * n + 2 * n + 2 * n))) return rc;
+  uint8_t *g1 = D.add(g1s, 3 * n), *g2 = D.add(g2s, 2 * n), *out = D.add(nullptr, 2 * n);
+  if ((rc = D.rc) || (rc = plk_pairing_batch_dev(g1, g2, n, out, nullptr))) return rc;
+  PLK_HIP(hipMemcpy(out_gt, out, 2 * n, hipMemcpyDeviceToHost));
   return PLK_OK;
 }
 
@@ -389,15 +412,11 @@ int plk_kzg_verify_batch(const plk_kzg_vk_t* vk, const uint8_t* commits3, const 
   VkWords w;
   int rc = check_n(fn, !vk || !commits3 || !zs || !ys || !proofs3 || !ok, n);
   if (rc || (rc = check_vk(fn, vk, &w)) || (rc = check_range(fn, n)) || (rc = plk_select_device())) return rc;
-  PlkScratch S;
-  if ((rc = S.alloc(fn, 9 * n))) return rc;
-  uint8_t *d_c = S.d, *d_w = S.d + 3 * n, *d_z = S.d + 6 * n, *d_y = S.d + 7 * n, *d_ok = S.d + 8 * n;
-  PLK_HIP(hipMemcpy(d_c, commits3, 3 * n, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_w, proofs3, 3 * n, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_z, zs, n, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_y, ys, n, hipMemcpyHostToDevice));
-  if ((rc = plk_kzg_verify_batch_dev(vk, d_c, d_z, d_y, d_w, n, d_ok, nullptr))) return rc;
-  PLK_HIP(hipMemcpy(ok, d_ok, n, hipMemcpyDeviceToHost));
+  Staged D;
+  if ((rc = D.alloc(fn, 3 * n + 3 * n + n + n + n))) return rc;
+  uint8_t *c = D.add(commits3, 3 * n), *p = D.add(proofs3, 3 * n), *z = D.add(zs, n), *y = D.add(ys, n), *o = D.add(nullptr, n);
+  if ((rc = D.rc) || (rc = plk_kzg_verify_batch_dev(vk, c, z, y, p, n, o, nullptr))) return rc;
+  PLK_HIP(hipMemcpy(ok, o, n, hipMemcpyDeviceToHost));
   return PLK_OK;
 }
 
@@ -421,16 +440,12 @@ int plk_kzg_verify_fold_batch(const plk_kzg_vk_t* vk, int k, const uint8_t* comm
   int rc = check_fold_verify(fn, vk, k, !commits3 || !weights || !ys || !zs || !proofs3 || !ok, n, &w);
   if (rc || (rc = plk_select_device())) return rc;
   const size_t e = n * (size_t)k;   // entries
-  PlkScratch S;
-  if ((rc = S.alloc(fn, 5 * e + 5 * n))) return rc;
-  uint8_t *d_c = S.d, *d_wt = S.d + 3 * e, *d_y = S.d + 4 * e, *d_w = S.d + 5 * e, *d_z = d_w + 3 * n, *d_ok = d_z + n;
-  PLK_HIP(hipMemcpy(d_c, commits3, 3 * e, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_wt, weights, e, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_y, ys, e, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_w, proofs3, 3 * n, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_z, zs, n, hipMemcpyHostToDevice));
-  if ((rc = plk_kzg_verify_fold_batch_dev(vk, k, d_c, d_wt, d_y, d_z, d_w, n, d_ok, nullptr))) return rc;
-  PLK_HIP(hipMemcpy(ok, d_ok, n, hipMemcpyDeviceToHost));
+  Staged D;
+  if ((rc = D.alloc(fn, 3 * e + e + e + 3 * n + n + n))) return rc;
+  uint8_t *c = D.add(commits3, 3 * e), *wt = D.add(weights, e), *y = D.add(ys, e), *p = D.add(proofs3, 3 * n),
+          *z = D.add(zs, n), *o = D.add(nullptr, n);
+  if ((rc = D.rc) || (rc = plk_kzg_verify_fold_batch_dev(vk, k, c, wt, y, z, p, n, o, nullptr))) return rc;
+  PLK_HIP(hipMemcpy(ok, o, n, hipMemcpyDeviceToHost));
   return PLK_OK;
 }
 
@@ -461,19 +476,12 @@ int plk_kzg_verify_multi_batch(const plk_kzg_vk_t* vk, int k, const uint8_t* com
   int rc = check_fold_verify(fn, vk, k, !commits3 || !sets || !weights || !ys || !us || !proofs6 || !ok, n, &w, PLK_KZG_MULTI_MAX);
   if (rc || (rc = plk_select_device())) return rc;
   const size_t e = n * (size_t)k;   // entries
-  PlkScratch S;
-  if ((rc = S.alloc(fn, 25 * e + 8 * n))) return rc;
-  // (the masks first: the allocation is aligned)
-  uint8_t *d_s = S.d, *d_c = d_s + 4 * e, *d_wt = d_c + 3 * e, *d_y = d_wt + e, *d_w = d_y + 17 * e, *d_u = d_w + 6 * n,
-          *d_ok = d_u + n;
-  PLK_HIP(hipMemcpy(d_s, sets, 4 * e, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_c, commits3, 3 * e, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_wt, weights, e, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_y, ys, 17 * e, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_w, proofs6, 6 * n, hipMemcpyHostToDevice));
-  PLK_HIP(hipMemcpy(d_u, us, n, hipMemcpyHostToDevice));
-  if ((rc = plk_kzg_verify_multi_batch_dev(vk, k, d_c, (const uint32_t*)d_s, d_wt, d_y, d_u, d_w, n, d_ok, nullptr))) return rc;
-  PLK_HIP(hipMemcpy(ok, d_ok, n, hipMemcpyDeviceToHost));
+  Staged D;
+  if ((rc = D.alloc(fn, 4 * e + 3 * e + e + SET_BITS * e + 6 * n + n + n))) return rc;
+  uint8_t *m = D.add(sets, 4 * e, 4), *c = D.add(commits3, 3 * e), *wt = D.add(weights, e), *y = D.add(ys, SET_BITS * e),
+          *p = D.add(proofs6, 6 * n), *u = D.add(us, n), *o = D.add(nullptr, n);
+  if ((rc = D.rc) || (rc = plk_kzg_verify_multi_batch_dev(vk, k, c, (const uint32_t*)m, wt, y, u, p, n, o, nullptr))) return rc;
+  PLK_HIP(hipMemcpy(ok, o, n, hipMemcpyDeviceToHost));
   return PLK_OK;
 }
 
