@@ -673,6 +673,64 @@ int plk_kzg_verify_multi_batch_dev(const plk_kzg_vk_t *vk /* HOST */, int k, con
                                    const uint8_t *d_us, const uint8_t *d_proofs6, size_t n, uint8_t *d_ok,
                                    void *stream);
 
+/* ---- KZG aggregate verification: a group of openings, one verdict -----------------------------
+ * The form a KZG verifier uses for many openings: a group of m openings (C_i, z_i, y_i, W_i) is checked
+ * with one linear combination under caller-chosen weights r_i and TWO pairings, instead of two pairings
+ * per opening.  Jobs lie in flat arrays exactly as for plk_kzg_verify_batch, plus one weight byte per job;
+ * a call holds n groups of m consecutive jobs each (m uniform over the call, as k is in
+ * plk_kzg_verify_fold_batch): group g owns jobs [g m, (g + 1) m).  The weights are the caller's, as
+ * everywhere in this library.
+ *
+ * CAVEAT.  An accepting aggregate is a statement about the WEIGHTED SUM of the group, not about each job:
+ * a job with r_i = 0 is not checked at all, and wrong jobs whose weighted errors cancel are accepted.  That
+ * the weights make this unlikely (independent, unpredictable to whoever produced the openings) is the
+ * caller's business; with 17 possible weights no choice makes it negligible.
+ *
+ * Semantics (the specification: the reference's raw formulas applied blindly, as plk_kzg_verify_batch
+ * applies them), group g:
+ *   accL = accW = g1_identity();
+ *   for i over the group's jobs in order:
+ *       yG = g1_mul(&G, y_i); nyG = g1_neg(&yG); zW = g1_mul(&W_i, z_i);      (G = vk->g1)
+ *       L = g1_add(&C_i, &nyG); L = g1_add(&L, &zW);
+ *       t = g1_mul(&L, r_i);   accL = g1_add(&accL, &t);
+ *       u = g1_mul(&W_i, r_i); accW = g1_add(&accW, &u);
+ *   ok[g] = gtp_equal(pairing(&accL, &vk->g2_1), pairing(&accW, &vk->g2_s))     1 or 0
+ * A group with an invalid byte (a G1 coordinate >= 101, a G1 flag > 1, z, y or r >= 17) gets ok[g] = 2; its
+ * neighbours are unaffected.  m = 1 with r = 1 is plk_kzg_verify_batch's byte (g1_mul(L, 1) =
+ * g1_add(identity, L) = L).
+ *
+ * Fast path: every C_i and W_i of the group and vk->g1 canonical group elements (the identity {0, 0, 1} or an
+ * on-curve affine point with flag 0: the MSM's notion).  Then accL and accW are EXP of two sums of discrete
+ * logs over the group's 9 bytes per job, and the group costs one streaming pass and two pairings.
+ *   _dev form (asynchronous on `stream`): a group that is valid but not canonical -- and every valid group
+ *   when vk->g1 is not canonical -- gets ok[g] = PLK_KZG_AGG_UNDECIDED (the `irregular` convention of
+ *   plk_msm_g1_dev); its neighbours are unaffected.  Exactly n bytes of d_ok are written.  Pointers may have
+ *   any alignment (the pass takes 16-byte loads in a group whose five arrays are 16-byte aligned at its first
+ *   job, byte loads otherwise, with the same result); d_work is 4-byte aligned.
+ *   Host form (synchronous): resolves those groups exactly -- the raw L_i, the library's exact raw fold over
+ *   (L, r) and (W, r), the two pairings -- so it is exact for every valid input and never returns 3.
+ * Geometry depends on (m, n) only.  plk_kzg_verify_agg_plan (host only, no device touched) reports it:
+ *   out[0]  path: 0 one lane per group (the pairings in that lane), 1 one wave per group, 2 out[1] blocks per group
+ *   out[1]  records per group in d_work (0 on path 0)
+ *   out[2]  blocks of the first launch
+ *   out[3]  launches: 1, or 2 -- the streaming pass, then one lane or wave per group finishing its records
+ * d_work: plk_kzg_verify_agg_workspace(m, n) bytes (16 per record), 0 exactly where the plan says one launch,
+ * and d_work may then be NULL.  Neither d_work nor d_ok needs initialisation: every word read was written by
+ * the same call, no atomics are used, a workspace may be reused by the next call on the stream, and calls on
+ * different streams with distinct workspaces may run concurrently.  Results are bit-identical from run to run.
+ * Errors (before any device query): a NULL pointer (d_work only where the workspace is not 0), m == 0, n == 0
+ * or an invalid byte in vk are PLK_ERR_ARG; m n > 2^30 is PLK_ERR_RANGE; the plan returns the same codes for
+ * (m, n) and the workspace function 0.  No GPU is PLK_ERR_NODEV -- there is no CPU fallback.  The device
+ * rules are those of plk_kzg_verify_batch(_dev). */
+#define PLK_KZG_AGG_UNDECIDED 3
+int    plk_kzg_verify_agg_plan(size_t m, size_t n, int64_t out[4]);          /* host only */
+size_t plk_kzg_verify_agg_workspace(size_t m, size_t n);                     /* host only; 0: bad args or none needed */
+int plk_kzg_verify_agg_batch(const plk_kzg_vk_t *vk, size_t m, const uint8_t *commits3, const uint8_t *zs,
+                             const uint8_t *ys, const uint8_t *proofs3, const uint8_t *rs, size_t n, uint8_t *ok /* n */);
+int plk_kzg_verify_agg_batch_dev(const plk_kzg_vk_t *vk /* HOST */, size_t m, const uint8_t *d_commits3,
+                                 const uint8_t *d_zs, const uint8_t *d_ys, const uint8_t *d_proofs3,
+                                 const uint8_t *d_rs, size_t n, uint8_t *d_ok, void *d_work, void *stream);
+
 /* ---- device-resident prover (replaces plonk_new / plonk_prove / plonk_free,
  * src/plonk.h:53-139, 223-656, 120-139) ---------------------------------------------------
  * plk_prover_create uploads the SRS and Z_H once (the PLONK struct of plonk_new); the

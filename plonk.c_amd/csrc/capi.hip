@@ -535,6 +535,13 @@ void plk_ctx_release(void) {
   if (g.live_provers > 0) g.live_provers--;
 }
 
+// The 102 meaningful words of the MSM lookup table E (msm.hip), for kernels outside msm.hip that take them as
+// an argument: E[y] for y < 101, then E[256] (the identity).  Written once by plk_init, constant after.
+void plk_group_ytab_words(uint32_t out[PLK_GROUP_ORDER]) {
+  memcpy(out, s_ytab, (PLK_GROUP_ORDER - 1) * sizeof(uint32_t));
+  out[PLK_GROUP_ORDER - 1] = s_ytab[256];
+}
+
 // A further device runs the library's kernels (a helper prover of plk_prover_attach_helpers):
 // its NTT root / column tables and the MSM __constant__ tables are built there once.  Returns
 // with the calling thread's current device unchanged.

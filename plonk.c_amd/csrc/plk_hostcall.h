@@ -28,6 +28,11 @@ inline int plk_select_device(void) {
   return PLK_OK;
 }
 
+// capi.hip: the 102 meaningful words of the MSM lookup table E (E[y] for y < 101, then E[256]) for a kernel
+// outside msm.hip, which cannot see that file's __constant__ copy.  Valid once the library is initialised
+// (after plk_use_device / plk_select_device returned PLK_OK); constant from then on.
+void plk_group_ytab_words(uint32_t out[102]);
+
 // device scratch of one host-buffer call, released on scope exit (hidden: its members are
 // no part of the library's exports)
 struct __attribute__((visibility("hidden"))) PlkScratch {

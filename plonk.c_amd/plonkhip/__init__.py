@@ -123,6 +123,10 @@ SIGNATURES = {
     "plk_kzg_verify_multi_batch": (C.c_int, [_vp, C.c_int, _u8p, C.POINTER(C.c_uint32), _u8p, _u8p, _u8p, _u8p, _sz,
                                              _u8p]),
     "plk_kzg_verify_multi_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "plk_kzg_verify_agg_plan": (C.c_int, [_sz, _sz, C.POINTER(C.c_int64)]),
+    "plk_kzg_verify_agg_workspace": (_sz, [_sz, _sz]),
+    "plk_kzg_verify_agg_batch": (C.c_int, [_vp, _sz, _u8p, _u8p, _u8p, _u8p, _u8p, _sz, _u8p]),
+    "plk_kzg_verify_agg_batch_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "plk_poly_lincomb_len": (_sz, [_vp]),
     "plk_poly_lincomb": (C.c_int, [_vp, C.POINTER(_sz)]),
     "plk_poly_lincomb_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -844,6 +848,52 @@ def kzg_verify_multi_dev(vk, k, commits, sets, weights, ys, us, proofs, n, ok, s
     (4 bytes each) 4-byte aligned; ok: n bytes"""
     _check("plk_kzg_verify_multi_batch_dev", lib().plk_kzg_verify_multi_batch_dev(
         C.byref(vk), int(k), _ptr(commits), _ptr(sets), _ptr(weights), _ptr(ys), _ptr(us), _ptr(proofs), int(n), _ptr(ok),
+        _stream(stream)))
+
+
+# ---------------------------------------------------------------- KZG aggregate verification
+PLK_KZG_AGG_UNDECIDED = 3
+KZG_AGG_PLAN_FIELDS = ("path", "slices", "blocks", "launches")
+
+
+def kzg_verify_agg_plan(m, n):
+    """plk_kzg_verify_agg_plan: the geometry of kzg_verify_agg_dev for n groups of m jobs -- path (0 one lane
+    per group, 1 one wave per group, 2 `slices` blocks per group), slices (records per group in the
+    workspace), blocks of the first launch, launches.  No device needed."""
+    out = (C.c_int64 * 4)()
+    _check("plk_kzg_verify_agg_plan", lib().plk_kzg_verify_agg_plan(int(m), int(n), out))
+    return dict(zip(KZG_AGG_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def kzg_verify_agg_workspace(m, n):
+    """plk_kzg_verify_agg_workspace: bytes of d_work for kzg_verify_agg_dev; 0 where the plan says one launch
+    and for bad arguments.  No device needed."""
+    return int(lib().plk_kzg_verify_agg_workspace(int(m), int(n)))
+
+
+def kzg_verify_agg(vk, m, commits, zs, ys, proofs, rs):
+    """plk_kzg_verify_agg_batch: n groups of m consecutive jobs (as kzg_verify's, plus a weight byte r per
+    job) -> n bytes, 1 the group's weighted sum accepts / 0 rejects / 2 an invalid byte in the group.  An
+    accept is a statement about the weighted sum, not about each job."""
+    c, w = _u8(commits).reshape(-1), _u8(proofs).reshape(-1)
+    za, ya, ra = _u8(zs).reshape(-1), _u8(ys).reshape(-1), _u8(rs).reshape(-1)
+    m = int(m)
+    e = za.size
+    if m <= 0 or e % m or c.size != 3 * e or w.size != 3 * e or ya.size != e or ra.size != e:
+        raise ValueError("n m commitments and proofs of 3 bytes, n m bytes of z, of y and of r")
+    n = e // m
+    ok = np.zeros(max(n, 1), np.uint8)
+    _check("plk_kzg_verify_agg_batch", lib().plk_kzg_verify_agg_batch(C.byref(vk), m, _p(c), _p(za), _p(ya), _p(w),
+                                                                      _p(ra), n, _p(ok)))
+    return ok[:n]
+
+
+def kzg_verify_agg_dev(vk, m, commits, zs, ys, proofs, rs, n, ok, work=None, stream=None):
+    """vk: a KzgVk on the host; the rest device tensors (or raw pointers) of any alignment; ok: n bytes, 3
+    (PLK_KZG_AGG_UNDECIDED) for a valid group that is not canonical; work: kzg_verify_agg_workspace(m, n)
+    device bytes, None where that is 0"""
+    _check("plk_kzg_verify_agg_batch_dev", lib().plk_kzg_verify_agg_batch_dev(
+        C.byref(vk), int(m), _ptr(commits), _ptr(zs), _ptr(ys), _ptr(proofs), _ptr(rs), int(n), _ptr(ok), _ptr(work),
         _stream(stream)))
 
 
