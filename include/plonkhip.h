@@ -731,6 +731,55 @@ int plk_kzg_verify_agg_batch_dev(const plk_kzg_vk_t *vk /* HOST */, size_t m, co
                                  const uint8_t *d_zs, const uint8_t *d_ys, const uint8_t *d_proofs3,
                                  const uint8_t *d_rs, size_t n, uint8_t *d_ok, void *d_work, void *stream);
 
+/* ---- KZG per-point openings: one polynomial at a point set, a proof each -----------------------
+ * The producer the aggregate verification consumes: polynomial i is opened at every point of its set S_i
+ * with a SEPARATE proof per point (vector commitments, data-availability samples: each position goes to a
+ * different verifier, so the multi-point scheme's one proof for the whole set is no use).  A set is a
+ * uint32_t mask as in the multi-point calls -- bit a set means a in S_i, bits 0 .. 16 only, at least one
+ * bit -- but here ALL 17 bits is allowed: no divisor is ever formed.
+ *
+ * Job order: polynomials in call order, within a polynomial its points ascending;
+ *   job e = sum_{i' < i} popcount(S_i') + rank of a in S_i,        J = sum_i popcount(S_i) jobs in all.
+ * Every output array is flat in that order, so (d_zs, d_ys, d_proofs3) -- with the commitment repeated per
+ * job, or a caller-made gather of it -- are the arguments of plk_kzg_verify_batch_dev and
+ * plk_kzg_verify_agg_batch_dev as they are, without a host round trip.
+ *
+ * Semantics (the specification): job e = (i, a) returns exactly (ys[b], proofs3[3 b ..]) of
+ * plk_kzg_open_batch on the expanded list whose entry b is (polys[i], lens[i], z = a); zs[e] = a where a zs
+ * array is given.  This holds for every coefficient byte and any SRS in the host form.  Quotients are not
+ * returned (plk_kzg_open_batch_dev stores them); len == 1 gives the identity proof and y = the coefficient.
+ *   Host form (synchronous): a polynomial with a byte >= 17, and every polynomial when plk_srs_irregular, is
+ *   recomputed by plk_kzg_open_batch itself on its expanded jobs.
+ *   _dev form (asynchronous on `stream`): d_status[e] = 0 and the exact bytes on the fast path (canonical
+ *   coefficients, regular SRS).  Every job of a polynomial with a byte >= 17 gets d_status = 1 and the proof
+ *   bytes FF FF FF, which the verify calls answer with 2, never with an accept; its d_ys are unspecified.
+ *   With an irregular SRS every job is flagged the same way while d_ys stay exact.  Neighbours are
+ *   unaffected.  Exactly J bytes of d_zs, d_ys and d_status and 3 J bytes of d_proofs3 are written.
+ * A polynomial's bytes and the SRS logs are read once for all its points (plus once more for the aggregates
+ * when it exceeds 4096 coefficients); PLK_KZG_POINTS_LAUNCH_POLYS polynomials travel per launch, larger
+ * batches run as consecutive launches on the stream.
+ * d_work: plk_kzg_points_workspace bytes -- 4 x (points + non-zero points of the set) x chunks of 4096 for a
+ * polynomial of more than one chunk, rounded up to 256 in all; 0 when every polynomial fits one chunk, and
+ * d_work may then be NULL.  It needs no initialisation: every word read was written by the same call, no
+ * atomics are used, it may be reused by the next call on the stream, and calls on different streams with
+ * distinct workspaces may run concurrently.  Results are bit-identical from run to run.  Pointers may have
+ * any alignment (d_work 4 bytes); 16-byte aligned polynomials take vector loads, with the same result.
+ * d_polys, lens and sets are HOST arrays, d_polys holds device pointers (as plk_kzg_open_batch_dev).
+ * Errors (all but the device check before any device query): a NULL handle or array (zs may be NULL), n <= 0,
+ * lens[i] == 0, or a mask that is 0 or has a bit above 16 are PLK_ERR_ARG; max(lens[i] - 1, 1) > plk_srs_len
+ * is PLK_ERR_RANGE with the reference's "degree exceeds SRS size" text; J > 2^30 is PLK_ERR_RANGE; a call
+ * from another device is PLK_ERR_ARG.  No GPU is PLK_ERR_NODEV -- there is no CPU fallback. */
+#define PLK_KZG_POINTS_LAUNCH_POLYS 64   /* polynomials one launch carries */
+size_t plk_kzg_points_count(const uint32_t *sets, int n);                         /* J; host only; 0: bad args */
+size_t plk_kzg_points_workspace(const size_t *lens, const uint32_t *sets, int n); /* host only; 0: bad args or none needed */
+int plk_kzg_open_points_batch(const plk_srs_t *s, const uint8_t *const *polys, const size_t *lens,
+                              const uint32_t *sets, int n,
+                              uint8_t *zs /* J or NULL */, uint8_t *ys /* J */, uint8_t *proofs3 /* 3 J */);
+int plk_kzg_open_points_batch_dev(const plk_srs_t *s, const uint8_t *const *d_polys, const size_t *lens,
+                                  const uint32_t *sets, int n,
+                                  uint8_t *d_zs /* J or NULL */, uint8_t *d_ys /* J */, uint8_t *d_proofs3 /* 3 J */,
+                                  uint8_t *d_status /* J */, void *d_work, void *stream);
+
 /* ---- device-resident prover (replaces plonk_new / plonk_prove / plonk_free,
  * src/plonk.h:53-139, 223-656, 120-139) ---------------------------------------------------
  * plk_prover_create uploads the SRS and Z_H once (the PLONK struct of plonk_new); the

@@ -1,6 +1,6 @@
-// Host pieces of the KZG opening family (kzg.hip, kzg_multi.hip): the resident SRS, the chunk geometry, the
-// argument checks the entry points share and the arena / read-back steps of the host-buffer forms.
-// One definition of each: the two files include this header and define none of them again.
+// Host pieces of the KZG opening family (kzg.hip, kzg_multi.hip, kzg_points.hip): the resident SRS, the chunk
+// geometry, the argument checks the entry points share and the arena / read-back steps of the host-buffer forms.
+// One definition of each: the three files include this header and define none of them again.
 // (Not for msm.hip or the headers it includes: bench.py hashes those.)
 #pragma once
 #include <string.h>

@@ -1,4 +1,5 @@
-// Device pieces of the KZG opening family (kzg.hip: commit, open, fold; kzg_multi.hip: multi-point).
+// Device pieces of the KZG opening family (kzg.hip: commit, open, fold; kzg_multi.hip: multi-point;
+// kzg_points.hip: per-point).
 // One definition of each: the opening kernels are these pieces around their own loads.
 // Everything is __forceinline__, so a kernel's code does not depend on which file it sits in.
 // (Not for msm.hip or the headers it includes: bench.py hashes those.)

@@ -127,6 +127,12 @@ SIGNATURES = {
     "plk_kzg_verify_agg_workspace": (_sz, [_sz, _sz]),
     "plk_kzg_verify_agg_batch": (C.c_int, [_vp, _sz, _u8p, _u8p, _u8p, _u8p, _u8p, _sz, _u8p]),
     "plk_kzg_verify_agg_batch_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "plk_kzg_points_count": (_sz, [C.POINTER(C.c_uint32), C.c_int]),
+    "plk_kzg_points_workspace": (_sz, [C.POINTER(_sz), C.POINTER(C.c_uint32), C.c_int]),
+    "plk_kzg_open_points_batch": (C.c_int, [_vp, C.POINTER(_u8p), C.POINTER(_sz), C.POINTER(C.c_uint32), C.c_int,
+                                            _u8p, _u8p, _u8p]),
+    "plk_kzg_open_points_batch_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(C.c_uint32), C.c_int,
+                                                _vp, _vp, _vp, _vp, _vp, _vp]),
     "plk_poly_lincomb_len": (_sz, [_vp]),
     "plk_poly_lincomb": (C.c_int, [_vp, C.POINTER(_sz)]),
     "plk_poly_lincomb_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -894,6 +900,53 @@ def kzg_verify_agg_dev(vk, m, commits, zs, ys, proofs, rs, n, ok, work=None, str
     device bytes, None where that is 0"""
     _check("plk_kzg_verify_agg_batch_dev", lib().plk_kzg_verify_agg_batch_dev(
         C.byref(vk), int(m), _ptr(commits), _ptr(zs), _ptr(ys), _ptr(proofs), _ptr(rs), int(n), _ptr(ok), _ptr(work),
+        _stream(stream)))
+
+
+# ---------------------------------------------------------------- KZG per-point openings
+PLK_KZG_POINTS_LAUNCH_POLYS = 64
+
+
+def kzg_points_count(sets):
+    """plk_kzg_points_count: J = the jobs of these sets (masks, bit a set: the point a; all 17 bits allowed);
+    0 for an invalid mask.  No device needed."""
+    return int(lib().plk_kzg_points_count(_u32s(sets), len(sets)))
+
+
+def kzg_points_workspace(lens, sets):
+    """plk_kzg_points_workspace: bytes of d_work for kzg_open_points_dev; 0 when every polynomial fits one
+    chunk and for bad arguments.  No device needed."""
+    n = len(lens)
+    if len(sets) != n:
+        raise ValueError("one set per polynomial")
+    ls = (_sz * max(n, 1))(*[int(v) for v in lens])
+    return int(lib().plk_kzg_points_workspace(ls, _u32s(sets), n))
+
+
+def kzg_open_points(srs, polys, sets):
+    """plk_kzg_open_points_batch: one set (mask) per polynomial -> ([z], [y], [proof 3 bytes]) flat in job
+    order (polynomials in order, within one its points ascending): what kzg_open returns on the expanded list"""
+    arrs, ptrs, lens, n = _host_polys(polys)
+    if len(sets) != n:
+        raise ValueError("one set per polynomial")
+    j = kzg_points_count(sets) if n else 0
+    zs = np.zeros(max(j, 1), np.uint8)
+    ys = np.zeros(max(j, 1), np.uint8)
+    out = np.zeros(3 * max(j, 1), np.uint8)
+    _check("plk_kzg_open_points_batch", lib().plk_kzg_open_points_batch(_srs_h(srs), ptrs, lens, _u32s(sets), n, _p(zs),
+                                                                        _p(ys), _p(out)))
+    return ([int(v) for v in zs[:j]], [int(v) for v in ys[:j]], [bytes(out[3 * i:3 * i + 3]) for i in range(j)])
+
+
+def kzg_open_points_dev(srs, d_polys, lens, sets, zs, ys, proofs3, status, work=None, stream=None):
+    """d_polys: device tensors (or raw pointers); lens, sets: host values; zs (or None), ys, status: J device
+    bytes, proofs3: 3 J, J = kzg_points_count(sets); work: kzg_points_workspace(lens, sets) device bytes, None
+    where that is 0."""
+    n = len(d_polys)
+    ptrs = (_vp * max(n, 1))(*[_ptr(p) for p in d_polys])
+    ls = (_sz * max(n, 1))(*[int(v) for v in lens])
+    _check("plk_kzg_open_points_batch_dev", lib().plk_kzg_open_points_batch_dev(
+        _srs_h(srs), ptrs, ls, _u32s(sets), n, _ptr(zs), _ptr(ys), _ptr(proofs3), _ptr(status), _ptr(work),
         _stream(stream)))
 
 
