@@ -185,6 +185,65 @@ int plk_msm_finalize_dev(const uint32_t *d_logs, int batch, int stride, uint8_t 
  * order) */
 int plk_dlog_generator(uint8_t out[3]);
 
+/* ---- Segmented MSM: a ragged list of MSMs in one call, flat 4-byte results ------------------
+ * Very many small or uneven sums over arbitrary points, with results the next call can read as they
+ * stand: the weighted sum of the commitments of a fold or multi-point job, the proofs of many provers
+ * combined in groups of different sizes.  One call takes any list of nseg consecutive segments of ONE
+ * flat point array (3 total bytes) and scalar array (total bytes) and returns one 4-byte word per segment.
+ *
+ * Segments.  Segment g is points and scalars [o_g, o_{g+1}).
+ *   uniform (d_offsets == NULL): o_g = g m; m >= 1 and total == m nseg.
+ *   ragged  (d_offsets != NULL): o_g = d_offsets[g], nseg + 1 words; m is ignored.  The offsets should
+ *           rise (not necessarily strictly) from any o_0 >= 0 to o_nseg <= total; bytes outside the
+ *           segments are not looked at for the results; an empty segment is legal.
+ * Results.  With status 0, d_out4[4 g ..] = {x, y, infinite, 0} are exactly the three bytes
+ *   plk_msm_g1(points + 3 o_g, scalars + o_g, o_{g+1} - o_g) returns: the reference's srs_eval_at_s fold
+ *   (src/srs.h:53-68), for ANY scalar byte (g1_mul takes the raw byte).  An empty segment gives the
+ *   identity {0, 0, 1}.
+ *   _dev form (asynchronous on `stream`): a segment holding a point that is not a canonical group element
+ *   in the MSM's sense ({0, 0, 1} or an on-curve affine point with flag 0) gets status
+ *   PLK_MSM_SEG_IRREGULAR and the bytes FF FF FF, which the verify calls answer with 2; a bad point flags
+ *   the segment that holds it and no other.  In ragged form every offset is read as min(o, total); a
+ *   segment with o_{g+1} < o_g or with an offset above total gets PLK_MSM_SEG_BAD and FF FF FF.  No offset
+ *   value whatever makes a kernel read outside [0, total) of the two arrays or outside the nseg + 1
+ *   offset words, and neighbours are unaffected.
+ *   Host form (synchronous): the offsets are validated on the host (a falling offset or one above total
+ *   is PLK_ERR_ARG before any device query) and irregular segments are resolved exactly with the
+ *   library's raw serial fold, as plk_msm_g1 does: the call is exact for every input byte and out3 (3
+ *   bytes per segment) needs no status.
+ * Geometry depends on (total, m, nseg, ragged) only.  plk_msm_g1_segments_plan (host only, no device
+ * touched) reports it:
+ *   out[0]  path: 0 lane (uniform, m <= 32: one lane per segment, one launch), 1 prefix (everything else:
+ *           a streaming pass over the POINT range stores scanned partial sums, a one-block scan of the
+ *           tile totals, then one lane per segment: at most 32 points summed from their bytes, a longer
+ *           segment as a difference of two prefixes)
+ *   out[1]  points per block tile of the first launch
+ *   out[2]  launches: 1 or 3
+ *   out[3]  blocks of the first launch
+ * The ragged form runs the streaming pass even when every segment is short: the library cannot know the
+ * lengths without reading device memory.
+ * d_work: plk_msm_g1_segments_workspace bytes (4 per 16 points + 8 per tile), 4-byte aligned, 0 exactly
+ * where the plan says one launch, and d_work may then be NULL.  Neither d_work nor d_out4 needs
+ * initialisation: every word read was written by the same call, no atomics are used, a workspace may be
+ * reused by the next call on the stream, and calls on different streams with distinct workspaces may run
+ * concurrently.  Results are bit-identical from run to run.  Exactly 4 nseg bytes of d_out4 are written.
+ * Points, scalars and out may have any alignment (offsets 4 bytes); 16-byte aligned points and scalars
+ * take vector loads, with the same result.
+ * Errors (all before any device query): a NULL pointer (d_work only where the workspace is not 0),
+ * nseg == 0, total == 0, or uniform with m == 0 or m nseg != total are PLK_ERR_ARG; total >= 2^32 or
+ * nseg > 2^30 is PLK_ERR_RANGE; the plan returns the same codes for its arguments and the workspace
+ * function 0.  No GPU is PLK_ERR_NODEV -- there is no CPU fallback.  The device rules are those of
+ * plk_kzg_verify_batch(_dev). */
+#define PLK_MSM_SEG_IRREGULAR 1   /* status: some encoding of the segment is not a canonical group element */
+#define PLK_MSM_SEG_BAD       2   /* status (_dev, ragged only): o[g+1] < o[g] or o[g+1] > total */
+int    plk_msm_g1_segments_plan(size_t total, size_t m, size_t nseg, int ragged, int64_t out[4]);  /* host only */
+size_t plk_msm_g1_segments_workspace(size_t total, size_t m, size_t nseg, int ragged);             /* host only; 0: bad args or none needed */
+int plk_msm_g1_segments_dev(const uint8_t *d_points /* 3 total */, const uint8_t *d_scalars /* total */, size_t total,
+                            const uint32_t *d_offsets /* DEVICE, nseg + 1 words, or NULL */, size_t m, size_t nseg,
+                            uint8_t *d_out4 /* 4 nseg */, void *d_work, void *stream);
+int plk_msm_g1_segments(const uint8_t *points, const uint8_t *scalars, size_t total,
+                        const uint32_t *offsets /* host, or NULL */, size_t m, size_t nseg, uint8_t *out3 /* 3 nseg */);
+
 /* poly_mul on device buffers: d_out holds la+lb-1 bytes (not overlapping d_a / d_b); *d_out_nz
  * receives the trimmed length (0 = the zero polynomial, i.e. length 1).  d_work:
  * plk_poly_mul_workspace() bytes.  d_a, d_b and d_out may have any alignment; exactly la and lb

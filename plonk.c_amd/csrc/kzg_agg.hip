@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "plk_device.h"
+#include "plk_g1log.h"
 #include "plk_hf17.h"
 #include "plk_hostcall.h"
 #include "plk_internal.h"
@@ -35,11 +36,14 @@
 namespace {
 
 using namespace plkpair;
+using plkg1log::TAB_C;
+using plkg1log::TAB_E;
+using plkg1log::dlog;
+using plkg1log::g1_word;
 
 constexpr uint32_t ORD = PLK_GROUP_ORDER;
 constexpr int AGG_T = PAIR_T;                  // threads per block (stage_inverses strides by PAIR_T)
 constexpr int AGG_WAVES = AGG_T / PLK_WAVE;
-constexpr int TAB_E = 128, TAB_C = 32;         // LDS table: entries x copies (16 KB)
 constexpr uint32_t F_INVALID = 1, F_IRREGULAR = 2;
 
 constexpr uint64_t AGG_LANE_MAX = 32;          // m <= : one lane per group
@@ -60,23 +64,6 @@ static_assert((uint64_t)TERM_MAX * 16 < (1ull << 32), "a 16-job step fits 32 bit
 struct AggTab { uint32_t w[ORD]; };            // E[y], y < 101, then E[256]
 struct AggIn { const uint8_t *c, *w, *z, *y, *r; };
 
-// the block's lookup table: entry e < 101 is E[e]; the rest never match (a y byte that differs from the index)
-__device__ __forceinline__ void stage_table(const AggTab& t, uint32_t* tab) {
-  for (uint32_t i = threadIdx.x; i < TAB_E * TAB_C / 4; i += AGG_T) {
-    const uint32_t e = i / (TAB_C / 4);
-    const uint32_t v = e < GFP ? t.w[e] : ((e ^ 1u) << 16);
-    reinterpret_cast<uint4*>(tab)[i] = make_uint4(v, v, v, v);
-  }
-}
-
-// d = E[idx] - k for the encoded point k = x << 8 | y << 16 | flag << 24: the log (< 102) exactly when the
-// encoding is canonical, >= 256 otherwise.  Any byte values are safe: the index is masked to the table.
-__device__ __forceinline__ uint32_t dlog(uint32_t k, const uint32_t* tab, uint32_t lane4) {
-  const uint32_t idx = (k >> 16) & (TAB_E - 1u);
-  const uint32_t e = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(tab) + ((idx << 7) | lane4));
-  return (((k >> 24) & 1u) ? (1u << 24) : e) - k;
-}
-
 __device__ __forceinline__ void job_term(uint32_t kc, uint32_t kw, uint32_t z, uint32_t y, uint32_t r, uint32_t nlg,
                                          const uint32_t* tab, uint32_t lane4, uint32_t& pl, uint32_t& pw, uint32_t& dor) {
   const uint32_t dc = dlog(kc, tab, lane4), dw = dlog(kw, tab, lane4);
@@ -95,16 +82,6 @@ __device__ __forceinline__ void job_bytes(const AggIn& in, uint64_t i, uint32_t 
   if (cx >= GFP || cy >= GFP || cf > 1u || wx >= GFP || wy >= GFP || wf > 1u || z >= HFP || y >= HFP || r >= HFP)
     flags |= F_INVALID;
   job_term(cx << 8 | cy << 16 | cf << 24, wx << 8 | wy << 16 | wf << 24, z, y, r, nlg, tab, lane4, pl, pw, dor);
-}
-
-// Encoded point j (0..15) of 48 point bytes held in w[0..11] (the byte string shifted up by one byte)
-template <int J>
-__device__ __forceinline__ uint32_t g1_word(const uint32_t (&w)[12]) {
-  constexpr int o = 3 * J, d = o >> 2, b = o & 3;
-  constexpr int d1 = (b + 2 <= 3) ? d : d + 1;
-  // v_perm_b32: selector bytes 0-3 pick from the 2nd operand, 4-7 from the 1st, 0x0C -> 0
-  constexpr uint32_t sel = 0x0Cu | ((uint32_t)b << 8) | ((uint32_t)(b + 1) << 16) | ((uint32_t)(b + 2) << 24);
-  return __builtin_amdgcn_perm(w[d1], w[d], sel);
 }
 
 // non-zero when one of 16 points holds a coordinate >= 101 or a flag >= 2 (additions and masks only).  A byte
@@ -224,7 +201,7 @@ __global__ __launch_bounds__(AGG_T) void agg_lane_kernel(AggTab t, AggIn in, VkW
                                                         uint8_t* __restrict__ okb) {
   __shared__ __attribute__((aligned(16))) uint32_t tab[TAB_E * TAB_C];
   __shared__ uint32_t invl[GFP];
-  stage_table(t, tab);
+  plkg1log::stage_table<AGG_T>(t, tab);
   stage_inverses(invl);   // (ends with the barrier)
   const G1Ops G{invl};
   const uint32_t lane4 = (threadIdx.x & (TAB_C - 1u)) << 2;
@@ -242,7 +219,7 @@ __global__ __launch_bounds__(AGG_T) void agg_stream_kernel(AggTab t, AggIn in, u
                                                           uint32_t* __restrict__ work) {
   __shared__ __attribute__((aligned(16))) uint32_t tab[TAB_E * TAB_C];
   __shared__ uint32_t part[AGG_WAVES][3];
-  stage_table(t, tab);
+  plkg1log::stage_table<AGG_T>(t, tab);
   __syncthreads();
   const uint32_t lane4 = (threadIdx.x & (TAB_C - 1u)) << 2;
   const uint32_t wave = threadIdx.x / PLK_WAVE, lane = threadIdx.x & (PLK_WAVE - 1);

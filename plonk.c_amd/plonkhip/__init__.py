@@ -46,6 +46,10 @@ SIGNATURES = {
     "plk_msm_combine_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "plk_msm_finalize_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "plk_dlog_generator": (C.c_int, [_u8p]),
+    "plk_msm_g1_segments_plan": (C.c_int, [_sz, _sz, _sz, C.c_int, C.POINTER(C.c_int64)]),
+    "plk_msm_g1_segments_workspace": (_sz, [_sz, _sz, _sz, C.c_int]),
+    "plk_msm_g1_segments_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "plk_msm_g1_segments": (C.c_int, [_u8p, _u8p, _sz, C.POINTER(C.c_uint32), _sz, _sz, _u8p]),
     "plk_poly_mul_workspace": (_sz, [_sz, _sz]),
     "plk_poly_mul_dev": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
     "plk_poly_mul_batch_workspace": (_sz, [_vp, C.c_int]),
@@ -900,6 +904,56 @@ def kzg_verify_agg_dev(vk, m, commits, zs, ys, proofs, rs, n, ok, work=None, str
     device bytes, None where that is 0"""
     _check("plk_kzg_verify_agg_batch_dev", lib().plk_kzg_verify_agg_batch_dev(
         C.byref(vk), int(m), _ptr(commits), _ptr(zs), _ptr(ys), _ptr(proofs), _ptr(rs), int(n), _ptr(ok), _ptr(work),
+        _stream(stream)))
+
+
+# ---------------------------------------------------------------- segmented MSM
+PLK_MSM_SEG_IRREGULAR = 1
+PLK_MSM_SEG_BAD = 2
+MSM_SEGMENTS_PLAN_FIELDS = ("path", "tile", "launches", "blocks")
+
+
+def msm_g1_segments_plan(total, m, nseg, ragged):
+    """plk_msm_g1_segments_plan: the geometry of msm_g1_segments_dev -- path (0 one lane per segment: uniform
+    m <= 32; 1 prefix: everything else), tile (points per block of the first launch), launches, blocks of the
+    first launch.  No device needed."""
+    out = (C.c_int64 * 4)()
+    _check("plk_msm_g1_segments_plan", lib().plk_msm_g1_segments_plan(int(total), int(m), int(nseg), int(bool(ragged)), out))
+    return dict(zip(MSM_SEGMENTS_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def msm_g1_segments_workspace(total, m, nseg, ragged):
+    """plk_msm_g1_segments_workspace: bytes of d_work for msm_g1_segments_dev; 0 where the plan says one launch
+    and for bad arguments.  No device needed."""
+    return int(lib().plk_msm_g1_segments_workspace(int(total), int(m), int(nseg), int(bool(ragged))))
+
+
+def msm_g1_segments(points, scalars, offsets=None, m=None):
+    """plk_msm_g1_segments: segment g = points and scalars [offsets[g], offsets[g + 1]) (ragged), or
+    [g m, (g + 1) m) with offsets None (uniform) -> an (nseg, 3) array, row g the bytes msm_g1 returns for
+    that segment, for every input byte."""
+    pts, sc = _u8(points).reshape(-1), _u8(scalars).reshape(-1)
+    total = sc.size
+    if pts.size != 3 * total:
+        raise ValueError("points must be n x 3 bytes for n scalars")
+    if offsets is None:
+        if m is None or int(m) <= 0 or total % int(m):
+            raise ValueError("uniform segments: m > 0 dividing the number of points")
+        m, nseg, off = int(m), total // int(m), None
+    else:
+        ov = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint32).reshape(-1))
+        m, nseg, off = 0, ov.size - 1, ov.ctypes.data_as(C.POINTER(C.c_uint32))
+    out = np.zeros((max(nseg, 1), 3), np.uint8)
+    _check("plk_msm_g1_segments", lib().plk_msm_g1_segments(_p(pts), _p(sc), total, off, m, max(nseg, 0), _p(out)))
+    return out[:max(nseg, 0)]
+
+
+def msm_g1_segments_dev(points, scalars, total, offsets, m, nseg, out4, work=None, stream=None):
+    """device tensors (or raw pointers) of any alignment; offsets: nseg + 1 uint32 words on the device, or None
+    for uniform segments of m points; out4: 4 nseg bytes {x, y, infinite, status}; work:
+    msm_g1_segments_workspace device bytes, None where that is 0"""
+    _check("plk_msm_g1_segments_dev", lib().plk_msm_g1_segments_dev(
+        _ptr(points), _ptr(scalars), int(total), _ptr(offsets), int(m), int(nseg), _ptr(out4), _ptr(work),
         _stream(stream)))
 
 
