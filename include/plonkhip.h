@@ -839,6 +839,75 @@ int plk_kzg_open_points_batch_dev(const plk_srs_t *s, const uint8_t *const *d_po
                                   uint8_t *d_zs /* J or NULL */, uint8_t *d_ys /* J */, uint8_t *d_proofs3 /* 3 J */,
                                   uint8_t *d_status /* J */, void *d_work, void *stream);
 
+/* ---- KZG flat batches: many short polynomials committed and opened in one launch ------------------
+ * The producer at the scale of the flat verify calls: vector commitments of a few dozen coefficients, the
+ * per-row commitments of a table, the openings of very many small provers.  One call takes npoly polynomials
+ * of at most PLK_KZG_FLAT_MAX coefficients each as consecutive segments of ONE flat coefficient array, with
+ * device-side descriptors, and is ONE kernel launch whatever npoly is.  Every output is a flat device array
+ * -- three bytes per G1, one byte per y and per status -- so (d_commits3, d_zs, d_ys, d_proofs3) of one
+ * plk_kzg_open_flat_dev call are the arguments of plk_kzg_verify_batch_dev and plk_kzg_verify_agg_batch_dev as
+ * they stand, without a host round trip.  (plk_kzg_commit_batch_dev / plk_kzg_open_batch_dev stay the calls for
+ * a few LONG polynomials; plk_msm_g1_segments serves arbitrary points, not the SRS prefix every polynomial
+ * needs here.)
+ *
+ * Segments, as in plk_msm_g1_segments.  Polynomial g is the bytes [o_g, o_{g+1}) of the flat array.
+ *   uniform (d_offsets == NULL): o_g = g m and total == m npoly.
+ *   ragged  (d_offsets != NULL): o_g = d_offsets[g], npoly + 1 words.  m is the largest length the caller
+ *           allows: the launch geometry must not depend on device data, so the library needs this bound --
+ *           and the list pays for it: bounded by m = 1024, a list whose polynomials are mostly short leaves
+ *           most lanes of its waves idle.  Bucket by length (m <= 32, <= 1024, <= 4096) for speed.
+ *   Every offset is read as min(o, total): no offset value whatever makes a kernel read outside [0, total)
+ *   of the coefficients or outside the npoly + 1 offset words.
+ * Semantics (the specification).  With status 0, polynomial g returns exactly the bytes plk_kzg_commit_batch
+ * or plk_kzg_open_batch return for the expanded list whose entry g is (coeffs + o_g, o_{g+1} - o_g, zs[g]);
+ * a length of 1 gives the identity proof and y = the coefficient.
+ *   _dev forms (asynchronous on `stream`; d_zs is a DEVICE array):
+ *     commitments are exact for ANY coefficient byte over a regular SRS (g1_mul takes the raw byte);
+ *     a polynomial holding a byte >= 17 gets status PLK_KZG_FLAT_IRREGULAR from the opening call, proof bytes
+ *       FF FF FF and an unspecified y; its commitment, where asked for, is still exact;
+ *     with an irregular SRS every polynomial gets PLK_KZG_FLAT_IRREGULAR and FF FF FF in both G1 outputs,
+ *       while the ys stay exact;
+ *     PLK_KZG_FLAT_BAD, FF FF FF in every G1 output and y = FF: a ragged polynomial that is empty, has
+ *       o_{g+1} < o_g, has an offset above total or is longer than m; and a polynomial whose device z byte is
+ *       >= 17 (the host cannot see that byte).
+ *     The verify calls answer FF FF FF with 2, never with an accept.  A flagged polynomial's neighbours are
+ *     unaffected.  Exactly npoly bytes of d_ys and d_status and 3 npoly bytes of each G1 output are written.
+ *   Host forms (synchronous): offsets and zs are validated on the host (each of the bad cases above is
+ *     PLK_ERR_ARG before any device query) and flagged polynomials are recomputed through plk_kzg_open_batch /
+ *     plk_kzg_commit_batch: the calls are exact for every byte and any SRS and need no status.
+ * Geometry depends on (m, npoly) only.  plk_kzg_flat_plan (host only, no device touched) reports it:
+ *   out[0]  path: 0 lane (m <= 32: one lane per polynomial), 1 wave (m <= 1024: one wave per polynomial,
+ *           sixteen coefficients per lane), 2 block (m <= 4096: one block per polynomial)
+ *   out[1]  polynomials per block: 256, 4 or 1
+ *   out[2]  blocks (capped at 2048: a block loops over the polynomials with the stride of the grid)
+ *   out[3]  launches: 1
+ * No workspace, no memset, no atomics, no records: every word read was written by the caller, results are
+ * bit-identical from run to run, and calls on different streams may run concurrently.  Pointers may have any
+ * alignment (offsets 4 bytes); aligned coefficients take 16-byte loads, with the same result.
+ * Errors.  The shape is checked first, then the pointers, then the SRS bound, then the device; all but the
+ * last before any device query.  PLK_ERR_ARG: npoly == 0, total == 0 or m == 0; uniform with m npoly != total;
+ * a NULL handle or a NULL required pointer; offsets off a 4-byte boundary; a call from another device.
+ * PLK_ERR_RANGE: m > PLK_KZG_FLAT_MAX; total >= 2^32; npoly > 2^30; commitments asked for with m > plk_srs_len
+ * or proofs with max(m - 1, 1) > plk_srs_len (the reference's "degree exceeds SRS size", on m as given).
+ * plk_kzg_flat_plan returns the same codes for its arguments (its total is m npoly in uniform form).  No GPU
+ * is PLK_ERR_NODEV -- there is no CPU fallback. */
+#define PLK_KZG_FLAT_MAX 4096        /* coefficients per polynomial (one chunk of the opening kernels) */
+#define PLK_KZG_FLAT_IRREGULAR 1     /* status: a coefficient byte >= 17 (openings), or an SRS without log form */
+#define PLK_KZG_FLAT_BAD       2     /* status (_dev): a broken ragged segment, or a device z byte >= 17 */
+int plk_kzg_flat_plan(size_t m, size_t npoly, int ragged, int64_t out[4]);            /* host only */
+int plk_kzg_commit_flat_dev(const plk_srs_t *s, const uint8_t *d_coeffs, size_t total,
+                            const uint32_t *d_offsets /* DEVICE, npoly + 1 words, or NULL */, size_t m, size_t npoly,
+                            uint8_t *d_commits3 /* 3 npoly */, uint8_t *d_status /* npoly */, void *stream);
+int plk_kzg_open_flat_dev(const plk_srs_t *s, const uint8_t *d_coeffs, size_t total,
+                          const uint32_t *d_offsets, size_t m, size_t npoly, const uint8_t *d_zs /* DEVICE, npoly */,
+                          uint8_t *d_ys /* npoly */, uint8_t *d_proofs3 /* 3 npoly */,
+                          uint8_t *d_commits3 /* 3 npoly, or NULL */, uint8_t *d_status /* npoly */, void *stream);
+int plk_kzg_commit_flat(const plk_srs_t *s, const uint8_t *coeffs, size_t total, const uint32_t *offsets /* host, or NULL */,
+                        size_t m, size_t npoly, uint8_t *commits3);
+int plk_kzg_open_flat(const plk_srs_t *s, const uint8_t *coeffs, size_t total, const uint32_t *offsets,
+                      size_t m, size_t npoly, const uint8_t *zs, uint8_t *ys, uint8_t *proofs3,
+                      uint8_t *commits3 /* or NULL */);
+
 /* ---- device-resident prover (replaces plonk_new / plonk_prove / plonk_free,
  * src/plonk.h:53-139, 223-656, 120-139) ---------------------------------------------------
  * plk_prover_create uploads the SRS and Z_H once (the PLONK struct of plonk_new); the

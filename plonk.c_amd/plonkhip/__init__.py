@@ -137,6 +137,11 @@ SIGNATURES = {
                                             _u8p, _u8p, _u8p]),
     "plk_kzg_open_points_batch_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(C.c_uint32), C.c_int,
                                                 _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plk_kzg_flat_plan": (C.c_int, [_sz, _sz, C.c_int, C.POINTER(C.c_int64)]),
+    "plk_kzg_commit_flat_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "plk_kzg_open_flat_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plk_kzg_commit_flat": (C.c_int, [_vp, _u8p, _sz, C.POINTER(C.c_uint32), _sz, _sz, _u8p]),
+    "plk_kzg_open_flat": (C.c_int, [_vp, _u8p, _sz, C.POINTER(C.c_uint32), _sz, _sz, _u8p, _u8p, _u8p, _u8p]),
     "plk_poly_lincomb_len": (_sz, [_vp]),
     "plk_poly_lincomb": (C.c_int, [_vp, C.POINTER(_sz)]),
     "plk_poly_lincomb_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -1002,6 +1007,76 @@ def kzg_open_points_dev(srs, d_polys, lens, sets, zs, ys, proofs3, status, work=
     _check("plk_kzg_open_points_batch_dev", lib().plk_kzg_open_points_batch_dev(
         _srs_h(srs), ptrs, ls, _u32s(sets), n, _ptr(zs), _ptr(ys), _ptr(proofs3), _ptr(status), _ptr(work),
         _stream(stream)))
+
+
+# ---------------------------------------------------------------- KZG flat batches
+PLK_KZG_FLAT_MAX = 4096
+PLK_KZG_FLAT_IRREGULAR = 1
+PLK_KZG_FLAT_BAD = 2
+KZG_FLAT_PLAN_FIELDS = ("path", "per_block", "blocks", "launches")
+
+
+def kzg_flat_plan(m, npoly, ragged=False):
+    """plk_kzg_flat_plan: the geometry of the flat calls -- path (0 one lane per polynomial: m <= 32; 1 one wave:
+    m <= 1024; 2 one block: m <= 4096), polynomials per block, blocks, launches (1).  No device needed."""
+    out = (C.c_int64 * 4)()
+    _check("plk_kzg_flat_plan", lib().plk_kzg_flat_plan(int(m), int(npoly), int(bool(ragged)), out))
+    return dict(zip(KZG_FLAT_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def _flat_host(coeffs, offsets, m):
+    co = _u8(coeffs).reshape(-1)
+    if offsets is None:
+        if m is None or int(m) <= 0 or co.size % int(m):
+            raise ValueError("uniform polynomials: m > 0 dividing the number of coefficients")
+        return co, None, None, int(m), co.size // int(m)
+    ov = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint32).reshape(-1))
+    if m is None:
+        m = int(np.diff(ov.astype(np.int64)).max()) if ov.size > 1 else 1
+    return co, ov, ov.ctypes.data_as(C.POINTER(C.c_uint32)), int(m), ov.size - 1
+
+
+def kzg_commit_flat(srs, coeffs, offsets=None, m=None):
+    """plk_kzg_commit_flat: polynomial g = coeffs[offsets[g]:offsets[g + 1]] (ragged; m the length bound, by
+    default the longest), or coeffs[g m:(g + 1) m] with offsets None -> an (npoly, 3) array, row g what
+    kzg_commit returns for that polynomial, for every input byte."""
+    co, keep, off, m, npoly = _flat_host(coeffs, offsets, m)
+    out = np.zeros((max(npoly, 1), 3), np.uint8)
+    _check("plk_kzg_commit_flat", lib().plk_kzg_commit_flat(_srs_h(srs), _p(co), co.size, off, m, max(npoly, 0), _p(out)))
+    return out[:max(npoly, 0)]
+
+
+def kzg_open_flat(srs, coeffs, zs, offsets=None, m=None, commits=False):
+    """plk_kzg_open_flat: the polynomials of kzg_commit_flat, polynomial g opened at zs[g] -> (ys, proofs) or
+    (ys, proofs, commitments): npoly bytes and (npoly, 3) arrays, what kzg_open / kzg_commit return on the
+    expanded list, for every input byte."""
+    co, keep, off, m, npoly = _flat_host(coeffs, offsets, m)
+    za = _u8(zs).reshape(-1)
+    if za.size != npoly:
+        raise ValueError("one z per polynomial")
+    ys = np.zeros(max(npoly, 1), np.uint8)
+    pr = np.zeros((max(npoly, 1), 3), np.uint8)
+    cm = np.zeros((max(npoly, 1), 3), np.uint8) if commits else None
+    _check("plk_kzg_open_flat", lib().plk_kzg_open_flat(_srs_h(srs), _p(co), co.size, off, m, max(npoly, 0), _p(za), _p(ys),
+                                                        _p(pr), _p(cm) if commits else None))
+    n = max(npoly, 0)
+    return (ys[:n], pr[:n], cm[:n]) if commits else (ys[:n], pr[:n])
+
+
+def kzg_commit_flat_dev(srs, coeffs, total, offsets, m, npoly, commits3, status, stream=None):
+    """device tensors (or raw pointers) of any alignment; offsets: npoly + 1 uint32 words on the device, or None
+    for uniform polynomials of m coefficients; commits3: 3 npoly bytes; status: npoly bytes"""
+    _check("plk_kzg_commit_flat_dev", lib().plk_kzg_commit_flat_dev(
+        _srs_h(srs), _ptr(coeffs), int(total), _ptr(offsets), int(m), int(npoly), _ptr(commits3), _ptr(status),
+        _stream(stream)))
+
+
+def kzg_open_flat_dev(srs, coeffs, total, offsets, m, npoly, zs, ys, proofs3, commits3, status, stream=None):
+    """as kzg_commit_flat_dev; zs, ys, status: npoly device bytes; proofs3: 3 npoly; commits3: 3 npoly or None.
+    (commits3, zs, ys, proofs3) are the arguments of kzg_verify_dev / kzg_verify_agg_dev as they stand."""
+    _check("plk_kzg_open_flat_dev", lib().plk_kzg_open_flat_dev(
+        _srs_h(srs), _ptr(coeffs), int(total), _ptr(offsets), int(m), int(npoly), _ptr(zs), _ptr(ys), _ptr(proofs3),
+        _ptr(commits3), _ptr(status), _stream(stream)))
 
 
 # ---------------------------------------------------------------- poly linear combinations
