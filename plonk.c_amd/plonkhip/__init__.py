@@ -142,6 +142,10 @@ SIGNATURES = {
     "plk_kzg_open_flat_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plk_kzg_commit_flat": (C.c_int, [_vp, _u8p, _sz, C.POINTER(C.c_uint32), _sz, _sz, _u8p]),
     "plk_kzg_open_flat": (C.c_int, [_vp, _u8p, _sz, C.POINTER(C.c_uint32), _sz, _sz, _u8p, _u8p, _u8p, _u8p]),
+    "plk_kzg_fold_flat_plan": (C.c_int, [_sz, _sz, _sz, C.c_int, C.POINTER(C.c_int64)]),
+    "plk_kzg_open_fold_flat_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plk_kzg_open_fold_flat": (C.c_int, [_vp, _u8p, _sz, C.POINTER(C.c_uint32), _sz, _sz, _sz, _u8p, _u8p, _u8p, _u8p,
+                                         _u8p]),
     "plk_poly_lincomb_len": (_sz, [_vp]),
     "plk_poly_lincomb": (C.c_int, [_vp, C.POINTER(_sz)]),
     "plk_poly_lincomb_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -1077,6 +1081,48 @@ def kzg_open_flat_dev(srs, coeffs, total, offsets, m, npoly, zs, ys, proofs3, co
     _check("plk_kzg_open_flat_dev", lib().plk_kzg_open_flat_dev(
         _srs_h(srs), _ptr(coeffs), int(total), _ptr(offsets), int(m), int(npoly), _ptr(zs), _ptr(ys), _ptr(proofs3),
         _ptr(commits3), _ptr(status), _stream(stream)))
+
+
+# ---------------------------------------------------------------- KZG flat folded openings
+def kzg_fold_flat_plan(m, k, ngroups, ragged=False):
+    """plk_kzg_fold_flat_plan: the geometry of the flat folded calls -- path (0 one lane per group: m <= 32; 1 one
+    wave: m <= 1024; 2 one block: m <= 4096), groups per block, blocks, launches (1).  No device needed."""
+    out = (C.c_int64 * 4)()
+    _check("plk_kzg_fold_flat_plan", lib().plk_kzg_fold_flat_plan(int(m), int(k), int(ngroups), int(bool(ragged)), out))
+    return dict(zip(KZG_FLAT_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def kzg_open_fold_flat(srs, coeffs, k, weights, zs, offsets=None, m=None, commits=False):
+    """plk_kzg_open_fold_flat: the polynomials of kzg_commit_flat in groups of k, group g = polynomials and weights
+    [k g, k (g + 1)) opened at zs[g] with one proof -> (ys, proofs) or (ys, proofs, commitments): npoly bytes,
+    (ngroups, 3) and (npoly, 3) arrays, what kzg_open_fold / kzg_commit return on the expanded groups, for every
+    input byte."""
+    co, keep, off, m, npoly = _flat_host(coeffs, offsets, m)
+    k = int(k)
+    if k <= 0 or npoly % k:
+        raise ValueError("k > 0 dividing the number of polynomials")
+    ng = npoly // k
+    wa, za = _u8(weights).reshape(-1), _u8(zs).reshape(-1)
+    if wa.size != npoly or za.size != ng:
+        raise ValueError("one weight per polynomial and one z per group")
+    ys = np.zeros(max(npoly, 1), np.uint8)
+    pr = np.zeros((max(ng, 1), 3), np.uint8)
+    cm = np.zeros((max(npoly, 1), 3), np.uint8) if commits else None
+    _check("plk_kzg_open_fold_flat", lib().plk_kzg_open_fold_flat(_srs_h(srs), _p(co), co.size, off, m, k, max(ng, 0), _p(wa),
+                                                                  _p(za), _p(ys), _p(pr), _p(cm) if commits else None))
+    n, g = max(npoly, 0), max(ng, 0)
+    return (ys[:n], pr[:g], cm[:n]) if commits else (ys[:n], pr[:g])
+
+
+def kzg_open_fold_flat_dev(srs, coeffs, total, offsets, m, k, ngroups, weights, zs, ys, proofs3, commits3, status,
+                           stream=None):
+    """device tensors (or raw pointers) of any alignment; offsets: k ngroups + 1 uint32 words on the device, or None
+    for uniform polynomials of m coefficients; weights, ys: k ngroups device bytes; zs, status: ngroups; proofs3:
+    3 ngroups; commits3: 3 k ngroups or None.  (commits3, weights, ys, zs, proofs3) are the arguments of
+    kzg_verify_fold_dev(vk, k, ..., n=ngroups) as they stand."""
+    _check("plk_kzg_open_fold_flat_dev", lib().plk_kzg_open_fold_flat_dev(
+        _srs_h(srs), _ptr(coeffs), int(total), _ptr(offsets), int(m), int(k), int(ngroups), _ptr(weights), _ptr(zs),
+        _ptr(ys), _ptr(proofs3), _ptr(commits3), _ptr(status), _stream(stream)))
 
 
 # ---------------------------------------------------------------- poly linear combinations
