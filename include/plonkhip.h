@@ -969,6 +969,75 @@ int plk_kzg_open_fold_flat(const plk_srs_t *s, const uint8_t *coeffs, size_t tot
                            size_t m, size_t k, size_t ngroups, const uint8_t *weights, const uint8_t *zs,
                            uint8_t *ys, uint8_t *proofs3, uint8_t *commits3 /* or NULL */);
 
+/* ---- KZG flat multi-point openings: many groups, each polynomial at its own point set, one launch ----
+ * The producer at the scale of plk_kzg_verify_multi_batch_dev: ngroups groups of k polynomials each, polynomial
+ * i of a group opened at every point of its own set S_i, the group answered by the two G1 elements W and W' of
+ * "KZG multi-point openings" above -- PLONK's round 5 as it really is (eight polynomials at {z}, one at
+ * {z, z omega}) for very many small provers.  The polynomials are the segments of ONE flat coefficient array
+ * exactly as in "KZG flat folded openings"; sets, weights and challenges are DEVICE arrays; the call is ONE
+ * kernel launch whatever ngroups, k and the sets are.  (plk_kzg_open_multi_batch_dev stays the call for a few
+ * groups of LONG polynomials, and the one that returns h.)
+ *
+ * Layout.  Polynomial e is the bytes [o_e, o_{e+1}) of the flat array: uniform (d_offsets == NULL) o_e = e m
+ * and total == m k ngroups; ragged k ngroups + 1 device offset words, m the largest length the caller allows,
+ * every offset read as min(o, total).  Group g owns polynomials, masks, weights and 17-byte ys rows
+ * [k g, k (g + 1)), the challenge us[g] and the six bytes proofs6[6 g ..] = W then W'; k is uniform over a
+ * call, 1 <= k <= PLK_KZG_MULTI_MAX.  Masks follow the rules of the multi-point calls: non-zero, bits 0 .. 16
+ * only, not all 17.  (d_commits3, d_sets, d_weights, d_ys, d_us, d_proofs6) of one call are the arguments of
+ * plk_kzg_verify_multi_batch_dev(vk, k, .., n = ngroups, ..) with nothing moved; d_sets is therefore 4-byte
+ * aligned.  h is not returned: there is no d_hs in the flat form.
+ * Semantics (the specification).  With status 0, group g returns exactly the bytes of the library's own host
+ * calls on the expanded group: ys[17 (k g + i) ..] and proofs6[6 g ..] those of plk_kzg_open_multi_batch for
+ * (the k polynomials, their masks, their weights, us[g]) -- all 17 bytes of a row are written, 0xFF off the
+ * set; len_i <= |S_i|, all weights zero, an h that cancels to zero or to a shorter degree, u inside T, outside
+ * T and u = 0, the point 0 in a set, a set of 16 points, polynomials of different lengths in a group and m = 1
+ * included -- and commits3[3 (k g + i) ..] that of plk_kzg_commit_batch.
+ *   _dev form (asynchronous on `stream`), one status byte per GROUP; a group's neighbours are never affected:
+ *     PLK_KZG_FLAT_BAD: a ragged polynomial of the group that is empty, falls, has an offset above total or is
+ *       longer than m; an invalid mask; a device weight byte >= 17; a device u byte >= 17.  Both proofs are
+ *       FF FF FF, every one of the group's 17 k ys bytes FF and every commitment of the group FF FF FF.
+ *     PLK_KZG_FLAT_IRREGULAR: a coefficient byte >= 17 anywhere in the group.  Both proofs are FF FF FF and the
+ *       group's ys are unspecified; its commitments are still exact (g1_mul takes the raw byte).
+ *     With an SRS that has no log form every group gets PLK_KZG_FLAT_IRREGULAR and FF FF FF in every G1
+ *       output; the ys stay exact wherever the coefficients are canonical.
+ *     Exactly 17 k ngroups bytes of d_ys, 6 ngroups of d_proofs6, ngroups of d_status and, when given,
+ *     3 k ngroups of d_commits3 are written.  No offset, mask, weight or u value makes a kernel read outside
+ *     the arrays as sized here.
+ *   Host form (synchronous): offsets, masks, weights and us are validated on the host (each of the BAD cases
+ *     above is PLK_ERR_ARG before any device query) and flagged groups are recomputed through
+ *     plk_kzg_open_multi_batch / plk_kzg_commit_batch: the call is exact for every byte and any SRS and needs
+ *     no status.
+ * Geometry depends on (m, k, ngroups, ragged) only -- in fact on (m, ngroups).  plk_kzg_multi_flat_plan (host
+ * only, no device touched) reports it, by the rule of plk_kzg_flat_plan:
+ *   out[0]  path: 0 lane (m <= 32: one lane per group), 1 wave (m <= 1024: one wave per group, sixteen
+ *           coefficients per lane), 2 block (m <= 4096: one block per group)
+ *   out[1]  groups per block: 256, 4 or 1
+ *   out[2]  blocks (capped at 2048: a block loops over the groups with the stride of the grid)
+ *   out[3]  launches: 1
+ * No workspace, no memset, no atomics, no records: every word read was written by the caller, results are
+ * bit-identical from run to run, and calls on different streams may run concurrently.  Coefficients and outputs
+ * may have any alignment (offsets and sets 4 bytes).
+ * Errors.  The shape is checked first, then the pointers, then the SRS bound, then the device; all but the
+ * last before any device query.  PLK_ERR_ARG: m, k, ngroups or total equal to 0; k > PLK_KZG_MULTI_MAX; uniform
+ * with m k ngroups != total; a NULL handle or a NULL required pointer; offsets or sets off a 4-byte boundary; a
+ * call from another device.  PLK_ERR_RANGE: m > PLK_KZG_FLAT_MAX; total >= 2^32; k ngroups > 2^30;
+ * max(m - 1, 1) > plk_srs_len, or m > plk_srs_len when commitments are asked for (Lh <= max(m - 1, 1), and W'
+ * commits at most max(m - 1, 1) quotient bytes).  plk_kzg_multi_flat_plan returns the same shape codes (its
+ * total is m k ngroups in uniform form).  No GPU is PLK_ERR_NODEV -- there is no CPU fallback. */
+int plk_kzg_multi_flat_plan(size_t m, size_t k, size_t ngroups, int ragged, int64_t out[4]);   /* host only */
+int plk_kzg_open_multi_flat_dev(const plk_srs_t *s, const uint8_t *d_coeffs, size_t total,
+                                const uint32_t *d_offsets /* DEVICE, k ngroups + 1 words, or NULL */,
+                                size_t m, size_t k, size_t ngroups,
+                                const uint32_t *d_sets /* DEVICE, k ngroups masks */,
+                                const uint8_t *d_weights /* DEVICE, k ngroups */,
+                                const uint8_t *d_us /* DEVICE, ngroups */,
+                                uint8_t *d_ys /* 17 k ngroups */, uint8_t *d_proofs6 /* 6 ngroups: W, W' */,
+                                uint8_t *d_commits3 /* 3 k ngroups, or NULL */, uint8_t *d_status /* ngroups */,
+                                void *stream);
+int plk_kzg_open_multi_flat(const plk_srs_t *s, const uint8_t *coeffs, size_t total, const uint32_t *offsets,
+                            size_t m, size_t k, size_t ngroups, const uint32_t *sets, const uint8_t *weights,
+                            const uint8_t *us, uint8_t *ys, uint8_t *proofs6, uint8_t *commits3 /* or NULL */);
+
 /* ---- device-resident prover (replaces plonk_new / plonk_prove / plonk_free,
  * src/plonk.h:53-139, 223-656, 120-139) ---------------------------------------------------
  * plk_prover_create uploads the SRS and Z_H once (the PLONK struct of plonk_new); the

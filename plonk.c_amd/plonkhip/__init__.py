@@ -146,6 +146,10 @@ SIGNATURES = {
     "plk_kzg_open_fold_flat_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "plk_kzg_open_fold_flat": (C.c_int, [_vp, _u8p, _sz, C.POINTER(C.c_uint32), _sz, _sz, _sz, _u8p, _u8p, _u8p, _u8p,
                                          _u8p]),
+    "plk_kzg_multi_flat_plan": (C.c_int, [_sz, _sz, _sz, C.c_int, C.POINTER(C.c_int64)]),
+    "plk_kzg_open_multi_flat_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "plk_kzg_open_multi_flat": (C.c_int, [_vp, _u8p, _sz, C.POINTER(C.c_uint32), _sz, _sz, _sz, C.POINTER(C.c_uint32), _u8p,
+                                          _u8p, _u8p, _u8p, _u8p]),
     "plk_poly_lincomb_len": (_sz, [_vp]),
     "plk_poly_lincomb": (C.c_int, [_vp, C.POINTER(_sz)]),
     "plk_poly_lincomb_batch_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -1123,6 +1127,51 @@ def kzg_open_fold_flat_dev(srs, coeffs, total, offsets, m, k, ngroups, weights, 
     _check("plk_kzg_open_fold_flat_dev", lib().plk_kzg_open_fold_flat_dev(
         _srs_h(srs), _ptr(coeffs), int(total), _ptr(offsets), int(m), int(k), int(ngroups), _ptr(weights), _ptr(zs),
         _ptr(ys), _ptr(proofs3), _ptr(commits3), _ptr(status), _stream(stream)))
+
+
+# ---------------------------------------------------------------- KZG flat multi-point openings
+def kzg_multi_flat_plan(m, k, ngroups, ragged=False):
+    """plk_kzg_multi_flat_plan: the geometry of the flat multi-point calls -- path (0 one lane per group: m <= 32;
+    1 one wave: m <= 1024; 2 one block: m <= 4096), groups per block, blocks, launches (1).  No device needed."""
+    out = (C.c_int64 * 4)()
+    _check("plk_kzg_multi_flat_plan", lib().plk_kzg_multi_flat_plan(int(m), int(k), int(ngroups), int(bool(ragged)), out))
+    return dict(zip(KZG_FLAT_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def kzg_open_multi_flat(srs, coeffs, k, sets, weights, us, offsets=None, m=None, commits=False):
+    """plk_kzg_open_multi_flat: the polynomials of kzg_commit_flat in groups of k, group g = polynomials, sets
+    (masks) and weights [k g, k (g + 1)) under the challenge us[g] -> (ys, proofs) or (ys, proofs, commitments):
+    (npoly, 17), (ngroups, 6) and (npoly, 3) arrays, what kzg_open_multi / kzg_commit return on the expanded
+    groups, for every input byte."""
+    co, keep, off, m, npoly = _flat_host(coeffs, offsets, m)
+    k = int(k)
+    if k <= 0 or npoly % k:
+        raise ValueError("k > 0 dividing the number of polynomials")
+    ng = npoly // k
+    sa = np.ascontiguousarray(np.asarray(sets, dtype=np.uint32).reshape(-1))
+    wa, ua = _u8(weights).reshape(-1), _u8(us).reshape(-1)
+    if sa.size != npoly or wa.size != npoly or ua.size != ng:
+        raise ValueError("one set and one weight per polynomial and one u per group")
+    ys = np.zeros((max(npoly, 1), 17), np.uint8)
+    pr = np.zeros((max(ng, 1), 6), np.uint8)
+    cm = np.zeros((max(npoly, 1), 3), np.uint8) if commits else None
+    _check("plk_kzg_open_multi_flat", lib().plk_kzg_open_multi_flat(
+        _srs_h(srs), _p(co), co.size, off, m, k, max(ng, 0), sa.ctypes.data_as(C.POINTER(C.c_uint32)), _p(wa), _p(ua),
+        _p(ys), _p(pr), _p(cm) if commits else None))
+    n, g = max(npoly, 0), max(ng, 0)
+    return (ys[:n], pr[:g], cm[:n]) if commits else (ys[:n], pr[:g])
+
+
+def kzg_open_multi_flat_dev(srs, coeffs, total, offsets, m, k, ngroups, sets, weights, us, ys, proofs6, commits3, status,
+                            stream=None):
+    """device tensors (or raw pointers) of any alignment, offsets and sets 4-byte aligned; offsets: k ngroups + 1
+    uint32 words on the device, or None for uniform polynomials of m coefficients; sets: k ngroups uint32 masks;
+    weights: k ngroups device bytes; ys: 17 k ngroups; us, status: ngroups; proofs6: 6 ngroups; commits3:
+    3 k ngroups or None.  (commits3, sets, weights, ys, us, proofs6) are the arguments of
+    kzg_verify_multi_dev(vk, k, ..., n=ngroups) as they stand."""
+    _check("plk_kzg_open_multi_flat_dev", lib().plk_kzg_open_multi_flat_dev(
+        _srs_h(srs), _ptr(coeffs), int(total), _ptr(offsets), int(m), int(k), int(ngroups), _ptr(sets), _ptr(weights),
+        _ptr(us), _ptr(ys), _ptr(proofs6), _ptr(commits3), _ptr(status), _stream(stream)))
 
 
 # ---------------------------------------------------------------- poly linear combinations
